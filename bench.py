@@ -7,6 +7,15 @@ over one resident batch of --units synthetic 4608-sample int16 blocks per GPU, p
 per-step stream statistics that are all-reduced over RCCL when N > 1.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--units U] [--config c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the workload).  --dump-outputs DIR also writes what the last timed step computed
+(a fixed, seeded sample of its units) as DIR/<name>.npy.  Everything else is measured only
+with --full, after the timed region: the per-kernel roofline (one-chunk calls of their own),
+the CPU oracle baseline, sampled parity against the oracle, the frame-writer and decoder legs
+and the end-to-end host encode; --cpu-seconds, --parity-units, --no-parity, --no-frames and
+--e2e-units select among those legs.
 
 For N > 1 one process runs per GPU.  Either the driver starts them with
 torch.distributed.run (WORLD_SIZE set), or `bench.py --gpus N` starts them itself: it
@@ -69,6 +78,13 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--open", type=int, default=0, choices=range(9), metavar="K",
                     help="K/8 of the units MA(1) near-white noise: the undecided-LPC workload (0 = the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel roofline, the CPU baseline, sampled "
+                         "parity, the frame-writer / decoder legs and the end-to-end encode (the options below "
+                         "select among them); off: the result line carries the metric and the workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (meta, residual, Rice parameters of a fixed, seeded "
+                         "sample of units, and the stream statistics) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
     ap.add_argument("--parity-units", type=int, default=64)
     ap.add_argument("--no-parity", action="store_true")
@@ -79,7 +95,10 @@ def parse(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="multi-rank plumbing only (CPU, gloo): self-launch, world-size check, shard "
                          "coverage and the stats all-reduce; prints a launch_check JSON line, no metric")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -557,6 +576,96 @@ def launch_check(args, cfg, units):
         dist.destroy_process_group()
 
 
+def result_head(args, cfg, world, value, elapsed, chunked, total_units, units, n, bits, comm, comm_note,
+                distributed, st):
+    """The result line of a plain run: the metric of the timed steps, the workload and the last
+    step's stream totals.  --full adds its legs to it (their keys are null in a plain run)."""
+    return {
+        "metric": METRIC,
+        "value": value,
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if chunked else "weak",
+        "vs_baseline": None,
+        "dtype": "i16 in; f64 autocorrelation/Levinson; i32 predictors",
+        "data": "synthetic: on-device integer generator (3 DDS tones + splitmix64 noise, SURVEY §8d)" +
+                (f"; {args.open}/8 of the units MA(1) near-white noise (--open)" if args.open else ""),
+        "full": bool(args.full),
+        "config": {"workload": cfg["workload"], "units_per_gpu": total_units // world,
+                   "units_total": total_units, "chunk_units": units if chunked else None, "block": n, "sample_bits": bits,
+                   "max_lpc_order": cfg["L"], "qlp_precision": cfg["q"], "rice": [cfg["rmin"], cfg["rmax"]],
+                   "mode": "fixed-only" if cfg["mode"] else "reference", "parallelism": f"dp{world} (block shards)",
+                   "open_eighths": args.open,
+                   "lpc_pruning": ("off: every LPC candidate's exact sum (FLACMI_NO_PRUNE=1)"
+                                   if os.environ.get("FLACMI_NO_PRUNE", "0") not in ("", "0") else
+                                   "on: candidates proven to lose skipped (sign bound, partial-sum tiers)"),
+                   "stats_collective": ("flacmi_allreduce_stats (C-ABI, RCCL)" if comm is not None else
+                                        f"torch.distributed all_reduce ({comm_note})" if distributed else None)},
+        "roofline": None, "kernels": None, "cpu_baseline": None, "frame_writer": None, "end_to_end": None,
+        "parity": None,
+        "stream_stats": {"units": int(st[0]), "samples": int(st[1]), "rice_bits": int(st[2]),
+                         "fixed": int(st[3]), "lpc": int(st[4]), "lpc_pruned": int(st[81]),
+                         "errors": int(st[65:80].sum()),
+                         # --full: meta.lpc_tiers of this rank's last batch: LPC candidate passes
+                         # made before the decision, as "passes/passes of the path": units
+                         "lpc_tiers": None},
+    }
+
+
+DUMP_BUDGET_BYTES = 48 << 20 # the .npy files of one --dump-outputs run, all together
+DUMP_MAX_UNITS = 1024
+
+
+def dump_outputs(path, meta, rparams, residual, stats, units, seed):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64
+    .npy files under `path`, for a fixed sample of the batch's units (drawn from `seed`, so
+    the same arguments give the same units and, the generator being seeded too, the same
+    inputs in every run and every build):
+      units.npy        [k]        the sampled unit indices within the batch, ascending
+      meta.npy         [k, F+32]  every scalar field of abi.META_DTYPE in declaration order
+                                  except lpc_tiers (a diagnostic of the pruning path taken),
+                                  then the 32 coefficient slots, zero past ncoefs
+      residual.npy     [k, W]     the zig-zag residual row, zero outside res_offset .. +res_len
+      rice_params.npy  [k, P]     the Rice parameters, zero past n_parts
+      stream_stats.npy [128]      the step's (all-reduced) stream statistics vector
+    Words of a row that the call leaves undefined (outside the ranges above) are zeroed, so
+    two runs compare file for file."""
+    import numpy as np
+    import torch
+
+    from flac_amd import abi
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stream_stats.npy"), stats.cpu().numpy().astype(np.float64))
+    if units <= 0:
+        return
+    scalars = [f for f in abi.META_DTYPE.names if f not in ("coefs", "lpc_tiers")]
+    ncoef = abi.META_DTYPE["coefs"].shape[0]
+    row_bytes = 8 * (1 + len(scalars) + ncoef + residual.shape[1] + rparams.shape[1])
+    k = max(1, min(units, DUMP_MAX_UNITS, DUMP_BUDGET_BYTES // row_bytes))
+    pick = np.sort(np.random.default_rng(seed).choice(units, size=k, replace=False))
+    idx = torch.as_tensor(pick, device=meta.device)
+    m = meta[idx].cpu().numpy().view(abi.META_DTYPE).reshape(k)
+    cols = np.arange(ncoef)[None, :]
+    coefs = np.where(cols < m["ncoefs"][:, None], m["coefs"], 0)
+    meta_f = np.concatenate([np.stack([m[f].astype(np.float64) for f in scalars], axis=1),
+                             coefs.astype(np.float64)], axis=1)
+    res = residual[idx].cpu().numpy().view(np.uint32)
+    cols = np.arange(res.shape[1])[None, :]
+    off, ln = m["res_offset"].astype(np.int64)[:, None], m["res_len"].astype(np.int64)[:, None]
+    res_f = np.where((cols >= off) & (cols < off + ln), res, 0).astype(np.float64)
+    par = rparams[idx].cpu().numpy()
+    cols = np.arange(par.shape[1])[None, :]
+    par_f = np.where(cols < m["n_parts"][:, None], par, 0).astype(np.float64)
+    np.save(os.path.join(path, "units.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "meta.npy"), meta_f)
+    np.save(os.path.join(path, "residual.npy"), res_f)
+    np.save(os.path.join(path, "rice_params.npy"), par_f)
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -661,6 +770,25 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     kt = az.timing()
     elapsed = reduce_elapsed(elapsed, dist, dev)
+    total_samples = total_units * n * args.steps
+    value = total_samples / elapsed
+    if args.dump_outputs and rank == 0:
+        # c4: the buffers hold the last chunk this rank analysed
+        last_units = units if not chunked else (min(units, total_units - my_chunks[-1] * units) if my_chunks else 0)
+        dump_outputs(args.dump_outputs, meta, rparams, residual, stats, last_units, args.seed)
+    if not args.full:
+        # the plain run: the metric of the timed steps and the workload, nothing measured besides
+        if rank == 0:
+            st = stats.cpu().numpy()
+            print(json.dumps(result_head(args, cfg, world, value, elapsed, chunked, total_units, units, n, bits,
+                                         comm, comm_note, distributed, st)), flush=True)
+        if comm is not None:
+            comm.close()
+        az.close()
+        if distributed:
+            dist.destroy_process_group()
+        return 0
+
     kt_steps, isolated_calls = kt, 0
     if cfg["L"] > 0 and not cfg["mode"] and get_knob("FLACMI_OVERLAP") != 0:
         # The library's default chunking overlaps k_lpc's last, partly filled round with
@@ -680,8 +808,6 @@ def main(argv=None):
 
     meta_np = meta.cpu().numpy().view(abi.META_DTYPE).reshape(units)
     st = stats.cpu().numpy()
-    total_samples = total_units * n * args.steps
-    value = total_samples / elapsed
 
     # ---- parity: sampled units vs the CPU oracle (outside the timed region) ----
     parity = None
@@ -755,30 +881,11 @@ def main(argv=None):
     if rank == 0:
         # rank 0 only, after the timed region (the other ranks are idle by then)
         cpu = cpu_baseline(cfg, args.cpu_seconds, args.seed, args.open) if args.cpu_seconds > 0 else None
-        line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if chunked else "weak",
-            "vs_baseline": None,
-            "dtype": "i16 in; f64 autocorrelation/Levinson; i32 predictors",
-            "data": "synthetic: on-device integer generator (3 DDS tones + splitmix64 noise, SURVEY §8d)" +
-                    (f"; {args.open}/8 of the units MA(1) near-white noise (--open)" if args.open else ""),
-            "config": {"workload": cfg["workload"], "units_per_gpu": total_units // world,
-                       "units_total": total_units, "chunk_units": units if chunked else None, "block": n, "sample_bits": bits,
-                       "max_lpc_order": cfg["L"], "qlp_precision": cfg["q"], "rice": [cfg["rmin"], cfg["rmax"]],
-                       "mode": "fixed-only" if cfg["mode"] else "reference", "parallelism": f"dp{world} (block shards)",
-                       "open_eighths": args.open,
-                       "lpc_pruning": ("off: every LPC candidate's exact sum (FLACMI_NO_PRUNE=1)"
-                                       if os.environ.get("FLACMI_NO_PRUNE", "0") not in ("", "0") else
-                                       "on: candidates proven to lose skipped (sign bound, partial-sum tiers)"),
-                       "stats_collective": ("flacmi_allreduce_stats (C-ABI, RCCL)" if comm is not None else
-                                            f"torch.distributed all_reduce ({comm_note})" if distributed else None)},
+        line = result_head(args, cfg, world, value, elapsed, chunked, total_units, units, n, bits, comm, comm_note,
+                           distributed, st)
+        line["stream_stats"]["lpc_tiers"] = {f"{t & 0xff}/{t >> 8}": int(c) for t, c in
+                                             zip(*np.unique(meta_np["lpc_tiers"], return_counts=True))}
+        line.update({
             "roofline": {"bound": "hbm", "kernel": dominant, "achieved": dom_gbs, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": dom_gbs / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": (os.path.relpath(tfile, REPO) + ": rocprofv3 FETCH_SIZE/WRITE_SIZE passes "
@@ -810,14 +917,7 @@ def main(argv=None):
             "frame_writer": frames,
             "end_to_end": e2e,
             "parity": parity,
-            "stream_stats": {"units": int(st[0]), "samples": int(st[1]), "rice_bits": int(st[2]),
-                             "fixed": int(st[3]), "lpc": int(st[4]), "lpc_pruned": int(st[81]),
-                             "errors": int(st[65:80].sum()),
-                             # meta.lpc_tiers of this rank's last batch: LPC candidate passes made
-                             # before the decision, as "passes/passes of the path": units
-                             "lpc_tiers": {f"{t & 0xff}/{t >> 8}": int(c) for t, c in
-                                           zip(*np.unique(meta_np["lpc_tiers"], return_counts=True))}},
-        }
+        })
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.close()

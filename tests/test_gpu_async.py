@@ -30,10 +30,24 @@ def test_analyze_device_returns_while_the_stream_is_busy():
         az.synth_device(x.data_ptr(), 2, 16, stride, 0, units, n, 2024, stream=s.cuda_stream)
         s.synchronize()
         p = make_params(12, 5, 0, 5)
+        # The batch is about a millisecond of GPU work, and a process's first call also loads
+        # the kernels' code objects and allocates the context's workspace, which takes the host
+        # longer than that.  So one call comes first, unmeasured, and each measured call is
+        # queued behind some 0.1 s of fills on the same stream: a call that returns without
+        # waiting for the stream finds it busy however slow the host is, and a call that
+        # waits for its own work waits for the fills before it and finds the stream idle.
+        with knob("FLACMI_OVERLAP", 0):
+            az.analyze_device(x.data_ptr(), 2, 16, stride, units, n, p, meta.data_ptr(), prm.data_ptr(),
+                              ps, res.data_ptr(), n, stream=s.cuda_stream)
+        s.synchronize()
+        pad = torch.empty(1 << 29, dtype=torch.int32, device=dev)
         runs = []
         for ov in (-(units // 2), 0):
             with knob("FLACMI_OVERLAP", ov):
                 for _ in range(2):  # the second call reuses the context's side stream
+                    with torch.cuda.stream(s):
+                        for _fill in range(192):
+                            pad.fill_(1)
                     az.analyze_device(x.data_ptr(), 2, 16, stride, units, n, p, meta.data_ptr(), prm.data_ptr(),
                                       ps, res.data_ptr(), n, stream=s.cuda_stream)
                     busy = not s.query()

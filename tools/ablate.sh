@@ -9,6 +9,6 @@ TAG=${1:-abl}; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for k in ${STOPS:-1 2 3 4 0}; do
-  FLACMI_DEBUG_STOP=$k timeout -k 10 300 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 --no-parity --no-frames --e2e-units 0 "$@" > $OUT/stop$k.json 2> $OUT/stop$k.err || { tail $OUT/stop$k.err; exit 1; }
+  FLACMI_DEBUG_STOP=$k timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --no-parity --no-frames --e2e-units 0 "$@" > $OUT/stop$k.json 2> $OUT/stop$k.err || { tail $OUT/stop$k.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/stop$k.json')); print('stop=$k', 'k_resid_ms %.3f' % d['kernels']['k_resid_ms'], 'k_lpc_ms %.3f' % d['kernels']['k_lpc_ms'])"
 done

@@ -7,6 +7,6 @@ TAG=${1:-pab}; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for k in ${MODES:-0 1 2 3}; do
-  FLACMI_PACK_ABLATE=$k timeout -k 10 300 python bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-parity --e2e-units 0 "$@" > $OUT/pab_$k.json 2>$OUT/pab_$k.err || { tail $OUT/pab_$k.err; exit 1; }
+  FLACMI_PACK_ABLATE=$k timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --no-parity --e2e-units 0 "$@" > $OUT/pab_$k.json 2>$OUT/pab_$k.err || { tail $OUT/pab_$k.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/pab_$k.json')); print('ablate=$k', 'frame_ms %.3f' % d['frame_writer']['ms_per_call'])"
 done

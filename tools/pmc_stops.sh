@@ -10,7 +10,7 @@ case $SET in
   *) echo "unknown set $SET"; exit 2;;
 esac
 mkdir -p $OUT
-ARGS="--units ${UNITS:-200000} --steps 2 --warmup 1 --cpu-seconds 0 --no-parity --no-frames $*"
+ARGS="--full --units ${UNITS:-200000} --steps 2 --warmup 1 --cpu-seconds 0 --no-parity --no-frames $*"
 for k in ${STOPS:-1 2 3 4 0}; do
   FLACMI_DEBUG_STOP=$k timeout -s KILL 120 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/s$k -o run -- python3 bench.py $ARGS > $OUT/s$k.json 2> $OUT/s$k.err || { echo "stop $k failed"; tail -5 $OUT/s$k.err; exit 1; }
   echo "== stop $k"; python3 tools/pmc_summary.py $OUT/s$k | grep -A9 ${KPAT:-k_resid_stream}
