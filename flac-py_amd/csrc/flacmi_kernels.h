@@ -127,7 +127,7 @@ struct DecodeArgs {
     int32_t defer_all;               /* knob FLACMI_DECODE_GENERIC: every frame through k_decode */
     unsigned long long* defer2_count; /* the frames k_decode_fx's LPC pass hands on: count, */
     int64_t* defer2_list;             /* and their indices ([n_frames]) */
-    int32_t lpc_pass;                 /* k_decode_fx's LPC pass runs (env FLACMI_DECODE_LPC=0: off) */
+    int32_t lpc_pass;                 /* k_decode_fx's LPC pass runs (knob FLACMI_DECODE_LPC=0: off) */
 };
 
 struct ResidLaunch {
@@ -141,7 +141,7 @@ ResidLaunch resid_launch_config(int n, int rmax_eff, int residual_bytes);
 constexpr int kMaxFinestParts = 4096;
 
 /* flacmi_set_knob's knobs: the environment's value (read once) or the last value set */
-enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobCount };
+enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobCount };
 int knob(Knob k);
 
 hipError_t launch_lpc(const LpcArgs& a, hipStream_t s);

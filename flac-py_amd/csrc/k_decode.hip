@@ -714,9 +714,10 @@ __device__ __forceinline__ bool decode_fx(const DecodeArgs& a, const int64_t f, 
         const int t = g.uint(6);
         /* LPC (LN > 0: orders up to LN) and invalid types: k_decode */
         if (!(t <= 1 || (t >= 8 && t <= 12) || (LN > 0 && t >= 32 && (t & 31) < LN))) {
-            /* worth the LPC pass: measured on 16-bit streams (config 2 open mixes 36.6 -> 25.4 ms);
-             * on config 3's open mix (24-bit stereo, L 32) it cost 103 -> 116 ms, so wider
-             * samples go straight to k_decode */
+            /* worth the LPC pass (knob FLACMI_DECODE_LPC, default on): orders <= kFxLpc (12) on
+             * streams of <= 16 bits (config 2 open mixes 36.6 -> 25.4 ms), orders <= kFxLpcW (32)
+             * on wider ones (config 3's open mix, 24-bit stereo, L 32: 103.5 -> 40.9 ms; an
+             * order-12 pass there had cost 103 -> 116 ms); the rest goes straight to k_decode */
             to_lpc = LN == 0 && t >= 32 && (t & 31) < (a.sample_size <= 16 ? kFxLpc : kFxLpcW);
             return false;
         }
@@ -1102,10 +1103,7 @@ hipError_t launch_decode(DecodeArgs a, hipStream_t s) {
             return hipGetLastError();
         };
         /* the listed frames again, with LPC subframes of order <= kFxLpc; the rest for k_decode */
-        static const bool lpc_pass = [] {
-            const char* v = getenv("FLACMI_DECODE_LPC");
-            return !(v && v[0] == '0');
-        }();
+        const bool lpc_pass = knob(kKnobDecodeLpc) != 0;
         a.lpc_pass = lpc_pass;
         if ((e = hipMemsetAsync(a.defer2_count, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
         if ((e = fx(std::integral_constant<int, 0>{})) != hipSuccess) return e;

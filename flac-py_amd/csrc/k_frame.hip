@@ -1368,6 +1368,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_packw2k(FrameArgs a) {
     packw_frame<1, 64, 512>(a);
 }
+/* knob 3 for samples of <= 16 bits: the 2 KB ring with 2048-value tiles (about 900 ring words
+ * at 14 bits a value), so ordinary 16-bit frames overrun the ring that ships several times each */
+__global__ __launch_bounds__(64) void k_packw2k_redo_test(FrameArgs a) {
+    packw_frame<4, 64, 512>(a);
+}
 
 hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
@@ -1398,7 +1403,8 @@ hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
     FrameArgs b = a;
     /* knob FLACMI_PACK_GENERIC: 1 every frame through k_pack; 2 no k_packw (k_pack32 for the
      * frames it fits, k_pack for the rest: the writer before k_packw); 3 k_packw with
-     * 2048-value tiles (tiles that overrun the ring: the test of its redo path); 6 / 8 k_packw
+     * 2048-value tiles on the ring the sample width ships with (512 words for samples of <= 16
+     * bits, 1024 for wider ones; tiles that overrun it: the test of its redo path); 6 / 8 k_packw
      * built for 256 / 128 threads (A/B); 7 as 2 with k_pack32 on its 16 KB window only.
      * Default: k_packw for every batch of 32-bit residual rows it can read with 16-byte loads
      * (one wave a frame beat k_pack32's one workgroup a frame on config 2 too: 8.02 against
@@ -1417,13 +1423,15 @@ hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
     b.ablate = ablate;
     if (vec_ok && !no_packw) {
         /* k_packw, 64 threads, 1 chunk a thread a tile (a tile of 512 values fits the ring
-         * above the < 128 words still waiting to leave up to 56 bits a value on average; a
-         * longer one, e.g. long unary runs of outliers, takes the redo path) */
+         * above the < 128 words still waiting to leave up to 56 bits a value on average on the
+         * 4 KB ring, 24 on the 2 KB ring of samples of <= 16 bits; a longer one, e.g. long
+         * unary runs of outliers, takes the redo path) */
         b.pack_split = 1;
         hipError_t e0 = hipMemsetAsync(b.slow_count, 0, sizeof(unsigned long long), s);
         if (e0 != hipSuccess) return e0;
         const dim3 g((unsigned)a.n_frames);
-        if (pack_generic == 3) hipLaunchKernelGGL(k_packw_redo_test, g, dim3(64), 0, s, b);
+        if (pack_generic == 3 && a.sample_size <= 16) hipLaunchKernelGGL(k_packw2k_redo_test, g, dim3(64), 0, s, b);
+        else if (pack_generic == 3) hipLaunchKernelGGL(k_packw_redo_test, g, dim3(64), 0, s, b);
         else if (pack_generic == 6) hipLaunchKernelGGL(k_packw256, g, dim3(kPackThreads), 0, s, b);
         else if (pack_generic == 8) hipLaunchKernelGGL(k_packw128, g, dim3(128), 0, s, b);
         else if (a.sample_size <= 16) hipLaunchKernelGGL(k_packw2k, g, dim3(64), 0, s, b);

@@ -457,8 +457,11 @@ int flacmi_timing_reset(flacmi_ctx* ctx);
  * every frame of flacmi_decode_frames_device through the general decoder kernel),
  * "FLACMI_PACK_GENERIC" (frame writer: 1 = every frame through the general writer kernel,
  * 2 = no ring-window writer (the one-window writer where a frame fits, else the general one),
- * 3 = the ring writer with 2048-value tiles, 6 / 8 = the ring writer built for 256 / 128
- * threads, 7 = as 2 with the one-window writer on its 16 KB window only).
+ * 3 = the ring writer with 2048-value tiles on the ring the sample width ships with (2 KB
+ * for samples of <= 16 bits, else 4 KB), 6 / 8 = the ring writer built for 256 / 128
+ * threads, 7 = as 2 with the one-window writer on its 16 KB window only), "FLACMI_DECODE_LPC"
+ * (0 = no second fast-decoder pass for LPC subframes: those frames go to the general decoder
+ * kernel; default 1).
  * FLACMI_E_INVALID for any other name.  No device needed. */
 int flacmi_set_knob(const char* name, int32_t value);
 int flacmi_get_knob(const char* name, int32_t* value);

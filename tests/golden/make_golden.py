@@ -358,6 +358,58 @@ def stream_set():
 
 
 # ---------------------------------------------------------------------------------
+# Burst streams: the recipe of tests/bursts.py restated without numpy (a quiet background plus
+# full-scale bursts; with -r 0,0 every loud value costs a long unary run).
+# ---------------------------------------------------------------------------------
+def burst_unit(n, bits, seed, index, background, events):
+    lo, out = -(1 << (bits - 1)), []
+    for i in range(n):
+        r = splitmix64(seed ^ ((index << 32) & M64) ^ i)
+        x = {"silence": 0, "alt1": 1 - 2 * (i & 1), "noise3": r % 7 - 3,
+             "sine": round(3000 * math.sin(2 * math.pi * (i & 2047) / 2048)) + (r >> 8) % 5 - 2}[background]
+        for ev in events:
+            if ev[0] == "burst" and ev[1] <= i < ev[1] + ev[2]:
+                mag = -lo - 1 - (r >> 8) % (1 << (bits - 4))
+                x = -mag if r & 1 else mag
+            elif ev[0] == "spike" and ev[1] == i:
+                x = ev[2] if len(ev) > 2 else lo
+        out.append(x)
+    return out
+
+
+def burst_set():
+    """Reference encode() output (len, sha256) of streams whose tiles overrun the device
+    writer's ring: -l 8, q = 12, -r 0,0; each channel is one burst_unit over the whole stream."""
+    import time
+    from flac.encoder import EncoderParameters, encode
+    B = ("burst",)
+    specs = {
+        "mono16": dict(frames=33768, block_size=16384, sample_size=16, sample_rate=44100, seed=61, channels=[
+            {"index": 0, "background": "noise3",
+             "events": [B + (4096, 512), B + (16384 + 6000, 512), B + (33768 - 300, 300)]}]),
+        "stereo16": dict(frames=33768, block_size=16384, sample_size=16, sample_rate=48000, seed=62, channels=[
+            {"index": 0, "background": "sine", "events": [B + (20480, 512)]},
+            {"index": 1, "background": "alt1", "events": [B + (8192, 512), B + (16384 + 8192, 512)]}]),
+        "mono24": dict(frames=2 * 32768 + 500, block_size=32768, sample_size=24, sample_rate=96000, seed=63, channels=[
+            {"index": 0, "background": "noise3", "events": [B + (16384, 512), B + (65536 - 512, 512)]}]),
+    }
+    out = {}
+    for name, sp in specs.items():
+        t0 = time.time()
+        chans = [burst_unit(sp["frames"], sp["sample_size"], sp["seed"], c["index"], c["background"],
+                            [tuple(e) for e in c["events"]]) for c in sp["channels"]]
+        p = EncoderParameters(block_size=sp["block_size"], rice_partition_order=range(0, 1),
+                              lpc_order=range(0, 9), qlp_precision=12)
+        data = b"".join(encode(sp["sample_rate"], sp["sample_size"], len(chans), sp["frames"],
+                               iter([list(v) for v in zip(*chans)]), p))
+        out[name] = dict(sp, max_lpc_order=8, qlp_precision=12, rice=[0, 0], len=len(data),
+                         sha256=hashlib.sha256(data).hexdigest(),
+                         samples_sha256=[samples_sha(c) for c in chans])
+        print(name, out[name]["len"], out[name]["sha256"], "%.1f s" % (time.time() - t0), flush=True)
+    return out
+
+
+# ---------------------------------------------------------------------------------
 # ACF-driven rows: the Levinson-Durbin / quantiser exception sites that integer PCM
 # never reaches (encoder.py:476 OverflowError of lambda_ ** 2, encoder.py:503
 # floor(log2(inf))), reached from autocorrelation vectors directly.  Each row runs the
@@ -450,6 +502,8 @@ def main(which):
         dump("edge.json", {"config": "edge cases and reference exceptions", "units": edge_set()})
     if "stream" in which:
         dump("streams.json", stream_set())
+    if "bursts" in which:
+        dump("bursts.json", burst_set())
     if "acf" in which:
         dump("acf_sites.json", {"config": "Levinson-Durbin / quantiser sites driven from ACF rows",
                                 "rows": acf_set()})

@@ -79,11 +79,13 @@ def test_knobs_set_get_and_reject_unknown_names():
     from flac_amd.analysis import get_knob, knob
     lib = load()
     for name in ("FLACMI_OVERLAP", "FLACMI_MF8_GRID", "FLACMI_STREAM_GENERIC", "FLACMI_DECODE_GENERIC",
-                 "FLACMI_PACK_GENERIC"):
+                 "FLACMI_PACK_GENERIC", "FLACMI_DECODE_LPC"):
         before = get_knob(name)
         with knob(name, 7):
             assert get_knob(name) == 7
         assert get_knob(name) == before
+    if "FLACMI_DECODE_LPC" not in os.environ:
+        assert get_knob("FLACMI_DECODE_LPC") == 1  # the fast decoder's LPC pass is on by default
     assert lib.flacmi_set_knob(b"FLACMI_NOPE", 1) == abi.E_INVALID
     assert b"unknown knob" in lib.flacmi_last_error()
     v = ctypes.c_int32(0)

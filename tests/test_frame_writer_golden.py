@@ -8,12 +8,15 @@ import math
 import numpy as np
 import pytest
 
+import bursts
 import frame_writer as FW
 import golden_util as G
 import oracle
 
 
-def _stream(pcm_channels, block, sample_rate, sample_size, L, q, rmin, rmax):
+def _stream(pcm_channels, block, sample_rate, sample_size, L, q, rmin, rmax, tiles=None):
+    """(len, sha256) of the stream; tiles (a list) receives the bit count of every 512-value
+    writer tile of every unit (bursts.tile_bits)."""
     chans = [np.asarray(c, dtype=np.int64) for c in pcm_channels]
     C, total = len(chans), len(chans[0])
     nb = (total + block - 1) // block
@@ -29,6 +32,10 @@ def _stream(pcm_channels, block, sample_rate, sample_size, L, q, rmin, rmax):
                                sample_bits=sample_size, threads=8)
     frames = FW.frames_from_analysis(rows, out, C, block, tail if n_tail else 0, sample_size, q)
     assert all(isinstance(f, bytes) for f in frames)
+    if tiles is not None:
+        for u in range(nb * C):
+            ln = tail if u >= (nb - 1) * C else block
+            tiles.extend(int(t) for t in bursts.tile_bits(out["meta"][u], out["rice_params"][u], out["residual"][u], ln))
     data = FW.stream_header(sample_rate, sample_size, C, total, block) + b"".join(frames)
     return len(data), hashlib.sha256(data).hexdigest()
 
@@ -53,6 +60,22 @@ def test_c3_stereo_stream():
     chans = [oracle.synth_unit(c["unit"], n, e["sample_size"], c["seed"]) for c in e["channels"]]
     got = _stream(chans, e["block_size"], e["sample_rate"], e["sample_size"], e["max_lpc_order"],
                   e["qlp_precision"], e["rice"][0], e["rice"][1])
+    assert got == (e["len"], e["sha256"])
+
+
+@pytest.mark.parametrize("name", ["mono16", "stereo16", "mono24"])
+def test_burst_streams(name):
+    """Streams whose Rice codes run to hundreds of zeros and whose 512-value tiles overrun
+    the device writer's LDS ring (tests/golden/bursts.json, reference encode() output): the
+    oracle pair gives the reference's bytes on the inputs the ring-overrun tests use."""
+    e = G.load("bursts.json")[name]
+    chans = [bursts.unit(e["frames"], e["sample_size"], e["seed"], c["index"], c["background"],
+                         [tuple(ev) for ev in c["events"]]) for c in e["channels"]]
+    assert [G.samples_sha(c) for c in chans] == e["samples_sha256"]
+    tiles = []
+    got = _stream(chans, e["block_size"], e["sample_rate"], e["sample_size"], e["max_lpc_order"],
+                  e["qlp_precision"], e["rice"][0], e["rice"][1], tiles=tiles)
+    assert max(tiles) >= 32 * 512, f"largest tile {max(tiles)} bits: no ring overrun in this stream"
     assert got == (e["len"], e["sha256"])
 
 

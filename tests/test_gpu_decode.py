@@ -6,8 +6,13 @@
 2. Round trip (BASELINE config 5 and the other config shapes): frames written by the
    device encoder decode on the device to exactly the source units, with CRC-8/16, frame
    numbers, frame ends and block sizes verified, and a corrupted byte is caught.
-Every test runs twice: with k_decode_fx taking the frames it accepts (the default) and with
-the FLACMI_DECODE_GENERIC knob sending every frame through the general k_decode.
+3. Burst streams (tests/bursts.py): Rice codes of up to 65536 zeros (FxReader::rice's loop
+   over many dwords, the restart of a lane that read past its look-ahead, the speculative
+   block's rollback, BitReader::rice's long-run loop) round-trip exactly, and a bit flipped
+   inside such a code is caught alike by both decoders.
+Every test runs three times: with k_decode_fx taking the frames it accepts (the default), with
+the FLACMI_DECODE_GENERIC knob sending every frame through the general k_decode, and with
+FLACMI_DECODE_LPC=0 (k_decode_fx without its LPC pass: LPC frames straight to k_decode).
 """
 import hashlib
 import json
@@ -16,6 +21,8 @@ import os
 import numpy as np
 import pytest
 
+import bursts
+import frame_writer as FW
 import oracle
 from flac_amd import abi
 from flac_amd.analysis import knob
@@ -24,11 +31,12 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "decode.json")
 
 
-@pytest.fixture(scope="module", params=["fx", "generic"])
+@pytest.fixture(scope="module", params=["fx", "generic", "fx_nolpc"])
 def az(request):
     from flac_amd.analysis import Analyzer
     a = Analyzer(0)
-    with knob("FLACMI_DECODE_GENERIC", int(request.param == "generic")):
+    with knob("FLACMI_DECODE_GENERIC", int(request.param == "generic")), \
+            knob("FLACMI_DECODE_LPC", int(request.param != "fx_nolpc")):
         yield a
     a.close()
 
@@ -74,21 +82,37 @@ ROUND_TRIP = {
 }
 
 
+BURST_ROUND_TRIP = sorted(set(bursts.CASES) - set(bursts.NO_DECODE))
+
+
 def _encode(az, name):
-    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, seed = ROUND_TRIP[name]
-    dt = np.int16 if bits <= 16 else np.int32
-    rows = oracle.synth_batch(seed * 1000, frames * C, n, bits, seed, dtype=dt)
-    n_tail = C if tail else 0
-    if tail:
-        rows[-C:, tail:] = 0
+    if name in bursts.CASES:
+        c = bursts.CASES[name]
+        C, n, tail, bits, ss, first = c["C"], c["n"], c["tail"], c["bits"], c["bits"], c["first"]
+        L, q, rmin, rmax, mode = c["L"], c["q"], c["rmin"], c["rmax"], c["mode"]
+        rows, n_tail = bursts.case_rows(name)
+    else:
+        frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, seed = ROUND_TRIP[name]
+        dt = np.int16 if bits <= 16 else np.int32
+        rows = oracle.synth_batch(seed * 1000, frames * C, n, bits, seed, dtype=dt)
+        n_tail = C if tail else 0
+        if tail:
+            rows[-C:, tail:] = 0
     params = oracle.make_params(L, q, rmin, rmax, mode)
+    if name in bursts.WRITER_ONLY:  # blocks the device analysis does not take: the oracle writer's frames
+        ora = oracle.analyze_batch(rows, params, n, tail, n_tail, sample_bits=bits, threads=8)
+        frames = FW.frames_from_analysis(rows, ora, C, n, tail, ss, q, first_frame=first)
+        assert all(isinstance(f, bytes) for f in frames)
+        data = np.frombuffer(b"".join(frames), dtype=np.uint8)
+        offsets = np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.int64)
+        return rows, data, offsets, (C, n, tail, n_tail, ss, first)
     data, offsets, status = az.encode_frames(rows, params, n, tail, n_tail, sample_bits=bits, channels=C,
                                              sample_size=ss, first_frame=first)
     assert not status.any(), "round-trip shapes are chosen so the reference writes every frame"
     return rows, data, offsets, (C, n, tail, n_tail, ss, first)
 
 
-@pytest.mark.parametrize("name", sorted(ROUND_TRIP))
+@pytest.mark.parametrize("name", sorted(ROUND_TRIP) + BURST_ROUND_TRIP)
 def test_round_trip_bit_exact(az, name):
     rows, data, offsets, (C, n, tail, n_tail, ss, first) = _encode(az, name)
     out, st, mm = az.decode_frames(data, offsets, C, ss, first_frame=first, expect=rows, block_len=n,
@@ -147,11 +171,11 @@ def test_fast_and_general_decoders_agree_on_damaged_streams(az):
     frames and bytes damaged at many places, the default split and the all-general run give
     the same status and mismatch count for every frame, and the same samples where status is 0."""
     rng = np.random.default_rng(5)
-    for name in ("lpc_heavy_q15", "c2", "wide20"):
+    for name in ("lpc_heavy_q15", "c2", "wide20", "burst16", "burst24_64k"):
         rows, data, offsets, (C, n, tail, n_tail, ss, first) = _encode(az, name)
         bad = data.copy()
         nf = len(offsets) - 1
-        hit = rng.choice(nf, size=max(3, nf // 4), replace=False)
+        hit = rng.choice(nf, size=min(nf, max(3, nf // 4)), replace=False)
         for f in hit:
             o0, o1 = int(offsets[f]), int(offsets[f + 1])
             pos = int(rng.integers(o0, o1))
@@ -168,3 +192,41 @@ def test_fast_and_general_decoders_agree_on_damaged_streams(az):
         for f in range(nf):
             if s0[f] == 0:
                 assert np.array_equal(o0[f * C:(f + 1) * C], o1[f * C:(f + 1) * C]), (name, f)
+
+
+def _both_decoders(az, bad, offsets, C, ss, first, rows, n):
+    res = {}
+    for gen in (0, 1):
+        with knob("FLACMI_DECODE_GENERIC", gen):
+            res[gen] = az.decode_frames(bad, offsets, C, ss, first_frame=first, expect=rows, block_len=n)
+    return res[0], res[1]
+
+
+@pytest.mark.parametrize("name,frame", [("lone16", 0), ("lone16_40k", 0), ("lone24_64k", 1)])
+def test_bit_flips_inside_a_long_rice_code(az, name, frame):
+    """A frame of digital silence with one full-scale sample holds one Rice code of 32767 to
+    65536 zeros.  Setting a bit in the middle of the run turns the code into two; clearing the
+    stop bit merges the run with the code behind it.  Either way the default split and the
+    all-general run give the same status and mismatch count for every frame, and the damaged
+    frame is never accepted silently (one flipped bit always changes the CRC-16)."""
+    rows, data, offsets, (C, n, tail, n_tail, ss, first) = _encode(az, name)
+    o0, o1 = int(offsets[frame]), int(offsets[frame + 1])
+    body = data[o0:o1]
+    # the run: the longest stretch of zero bytes of the frame (the other codes are "1" + p bits)
+    nz = np.flatnonzero(body)
+    gaps = np.diff(nz)
+    k = int(gaps.argmax())
+    start, stop = int(nz[k]) + 1, int(nz[k + 1])  # zero bytes [start, stop), the stop bit in byte stop
+    assert stop - start >= 4000 and start >= 7
+    cases = {"split": (start + (stop - start) // 2, 0x10, "set"),
+             "merge": (stop, 1 << (int(body[stop]).bit_length() - 1), "clear")}
+    for what, (pos, bit, op) in cases.items():
+        bad = data.copy()
+        assert bool(bad[o0 + pos] & bit) == (op == "clear")
+        bad[o0 + pos] ^= np.uint8(bit)
+        (out0, s0, m0), (out1, s1, m1) = _both_decoders(az, bad, offsets, C, ss, first, rows, n)
+        assert np.array_equal(s0, s1), (what, [hex(int(v)) for v in s0], [hex(int(v)) for v in s1])
+        assert np.array_equal(m0, m1), (what, m0, m1)
+        assert s0[frame] != 0 or m0[frame] > 0, what
+        others = [f for f in range(len(offsets) - 1) if f != frame]
+        assert not s0[others].any() and not m0[others].any(), what

@@ -4,10 +4,14 @@ tests/test_frame_writer_golden.py): every frame byte-identical, on the oracle's 
 analysis of the same units, for the BASELINE config shapes and the header / writer edge
 cases (explicit 8/16-bit block sizes, 1..6-byte coded numbers, frames larger than the
 kernel's 16 KB LDS window, Rice5Bit, frame-number overflow, the q = 16 writer assert), and
-frames that k_pack32 hands to the general k_pack."""
+frames that k_pack32 hands to the general k_pack, and the burst inputs of tests/bursts.py:
+frames whose 512-value tiles overrun k_packw's LDS ring (the redo path of the 512-word ring
+that ships for samples of <= 16 bits and of the 1024-word ring of wider ones, at MAXC = 1),
+each asserted to overrun from the oracle's analysis before any device byte is compared."""
 import numpy as np
 import pytest
 
+import bursts
 import frame_writer as FW
 import oracle
 from flac_amd import abi
@@ -56,14 +60,82 @@ def _rows(frames, C, n, tail, bits, seed):
     return rows, (C if tail else 0)
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
+BURSTS = sorted(bursts.CASES)
+ALL = sorted(CASES) + BURSTS
+
+
+def _case(name):
+    """(frames, C, n, tail, bits, L, q, rmin, rmax, mode, sample_size, first_frame, rows, n_tail) of a
+    CASES row or of a burst case (tests/bursts.py)."""
+    if name in CASES:
+        frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, seed = CASES[name]
+        rows, n_tail = _rows(frames, C, n, tail, bits, seed)
+    else:
+        c = bursts.CASES[name]
+        C, n, tail, bits, ss, first = c["C"], c["n"], c["tail"], c["bits"], c["bits"], c["first"]
+        L, q, rmin, rmax, mode = c["L"], c["q"], c["rmin"], c["rmax"], c["mode"]
+        rows, n_tail = bursts.case_rows(name)
+        frames = rows.shape[0] // C
+    return frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, rows, n_tail
+
+
+def _write_from_oracle(az, rows, ora, params, C, n, ss, q, first):
+    """The device frame writer alone on the oracle's analysis (flacmi_frame_sizes_device +
+    flacmi_pack_frames_device on device buffers): (frame bytes, offsets, status).  For blocks
+    the analysis kernels do not take."""
+    import torch
+    from flac_amd.analysis import device_batch, frame_params
+    dev = torch.device("cuda", 0)
+    units = rows.shape[0]
+    meta = ora["meta"]
+    assert (meta["res_offset"] == meta["order"]).all()  # the residual rows are indexed by sample
+    assert int(ora["residual"].max()) < 1 << 32
+    stride = (n + 3) // 4 * 4
+    res = np.zeros((units, stride), dtype=np.uint32)
+    res[:, :n] = ora["residual"][:, :n].astype(np.uint32)
+    rp = np.ascontiguousarray(ora["rice_params"], dtype=np.int32)
+    pst = rp.shape[1]
+    s = torch.as_tensor(np.ascontiguousarray(rows), device=dev)
+    d_meta = torch.from_numpy(np.frombuffer(meta.tobytes(), dtype=np.uint8).copy()).to(dev)
+    d_rp = torch.from_numpy(rp).to(dev)
+    d_res = torch.from_numpy(res.view(np.int32)).to(dev)
+    frames = units // C
+    off = torch.empty(frames + 1, dtype=torch.int64, device=dev)
+    st = torch.empty(frames, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    b = device_batch(s.data_ptr(), rows.dtype.itemsize, ss, rows.shape[1], units, n)
+    fp = frame_params(C, ss, q, first)
+    az.frame_sizes_device(b, fp, d_meta.data_ptr(), d_rp.data_ptr(), pst, off.data_ptr(), st.data_ptr(), stream)
+    torch.cuda.synchronize(dev)
+    offsets = off.cpu().numpy()
+    out = torch.zeros(int(offsets[-1]) + 64, dtype=torch.uint8, device=dev)
+    az.pack_frames_device(b, fp, d_meta.data_ptr(), d_rp.data_ptr(), pst, d_res.data_ptr(), 4, stride,
+                          off.data_ptr(), st.data_ptr(), out.data_ptr(), out.numel(), stream)
+    torch.cuda.synchronize(dev)
+    host = out.cpu().numpy()
+    assert not host[int(offsets[-1]):].any()  # nothing written behind the last frame
+    return host[: int(offsets[-1])], offsets, st.cpu().numpy()
+
+
+def _encode(az, name, rows, params, n, tail, n_tail, bits, C, ss, q, first, ora=None):
+    """The case's frames from the device: the whole encoder, or for bursts.WRITER_ONLY the
+    writer on the oracle's analysis."""
+    if name in bursts.WRITER_ONLY:
+        if ora is None:
+            ora = oracle.analyze_batch(rows, params, n, tail, n_tail, sample_bits=bits, threads=8)
+        return _write_from_oracle(az, rows, ora, params, C, n, ss, q, first)
+    return az.encode_frames(rows, params, n, tail, n_tail, sample_bits=bits, channels=C, sample_size=ss,
+                            first_frame=first)
+
+
+@pytest.mark.parametrize("name", ALL)
 def test_frames_match_oracle_writer(az, name):
-    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, seed = CASES[name]
-    rows, n_tail = _rows(frames, C, n, tail, bits, seed)
+    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, rows, n_tail = _case(name)
     params = oracle.make_params(L, q, rmin, rmax, mode)
-    data, offsets, status = az.encode_frames(rows, params, n, tail, n_tail, sample_bits=bits, channels=C,
-                                             sample_size=ss, first_frame=first)
     ora = oracle.analyze_batch(rows, params, n, tail, n_tail, sample_bits=bits, threads=8)
+    if name in bursts.CASES:  # the overrun conditions, from the oracle alone, before any device byte
+        bursts.check_expectations(name, ora)
+    data, offsets, status = _encode(az, name, rows, params, n, tail, n_tail, bits, C, ss, q, first, ora)
     want = FW.frames_from_analysis(rows, ora, C, n, tail, ss, q, first_frame=first)
     assert len(offsets) == frames + 1 and offsets[0] == 0
     for f, w in enumerate(want):
@@ -128,37 +200,40 @@ def test_device_pointer_path_matches_host_path(az):
 
 @pytest.mark.parametrize("gen", [1, 2, 3, 7])
 @pytest.mark.parametrize("name", ["c2", "c1_tail", "bs16_3ch", "c3_stereo", "c3_tail", "wide20", "wide_odd",
-                                  "wide_fine", "wide16_tail", "big3ch_list", "c5_fixed", "bs8_coded6"])
+                                  "wide_fine", "wide16_tail", "big3ch_list", "c5_fixed", "bs8_coded6"] + BURSTS)
 def test_general_writer_alone_matches(az, name, gen):
     """Knob FLACMI_PACK_GENERIC=1 (every frame through the general k_pack) and =2 (k_packw
     off: k_pack32 for the frames it fits, k_pack for the rest) give the default path's bytes
     (k_packw for every 32-bit batch); the c3 frames exercise k_packw's ring against k_pack,
     and =3 (k_packw with tiles of 2048
     values, about 1400 ring words for these 24-bit frames) its redo of a segment that
-    overruns the 1024-word ring; =7 keeps k_pack32 on its 16 KB window (the default takes
+    overruns the 1024-word ring; for samples of <= 16 bits =3 runs the 2048-value tiles on
+    the 512-word ring that ships for them (about 900 words at 14 bits a value: every ordinary
+    16-bit case overruns it several times a frame); the burst cases overrun the default
+    path's ring as well; =7 keeps k_pack32 on its 16 KB window (the default takes
     the 12 KB window when a verbatim frame fits it with a quarter to spare)."""
-    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, seed = CASES[name]
-    rows, n_tail = _rows(frames, C, n, tail, bits, seed)
+    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, rows, n_tail = _case(name)
     params = oracle.make_params(L, q, rmin, rmax, mode)
-    want = az.encode_frames(rows, params, n, tail, n_tail, sample_bits=bits, channels=C, sample_size=ss,
-                            first_frame=first)
+    ora = None
+    if name in bursts.WRITER_ONLY:
+        ora = oracle.analyze_batch(rows, params, n, tail, n_tail, sample_bits=bits, threads=8)
+    want = _encode(az, name, rows, params, n, tail, n_tail, bits, C, ss, q, first, ora)
     with knob("FLACMI_PACK_GENERIC", gen):
-        got = az.encode_frames(rows, params, n, tail, n_tail, sample_bits=bits, channels=C, sample_size=ss,
-                               first_frame=first)
+        got = _encode(az, name, rows, params, n, tail, n_tail, bits, C, ss, q, first, ora)
     assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
     assert got[0].tobytes() == want[0].tobytes()
 
 
 @pytest.mark.parametrize("name,upb", [("c2", 5), ("c1_tail", 4), ("c3_stereo", 2), ("bs16_3ch", 3),
                                       ("q16_assert", 12), ("wide20", 4), ("big3ch_list", 6),
-                                      ("wide_odd", 2), ("wide16_tail", 2)])
+                                      ("wide_odd", 2), ("wide16_tail", 2)] +
+                         [(b, bursts.CASES[b]["upb"]) for b in BURSTS if b not in bursts.WRITER_ONLY])
 def test_encode_pipeline_equals_encode_frames(az, name, upb):
     """flacmi_encode_pipeline (sub-batches of upb frames, three in flight, the caller's
     buffers page-locked in place) gives the bytes, offsets and statuses of the one-shot
     flacmi_encode_host path, including the short last frame, the writer's own asserts
     and the 64-bit-residual redo; the rows are a strided view (row stride > block)."""
-    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, seed = CASES[name]
-    rows, n_tail = _rows(frames, C, n, tail, bits, seed)
+    frames, C, n, tail, bits, L, q, rmin, rmax, mode, ss, first, rows, n_tail = _case(name)
     params = oracle.make_params(L, q, rmin, rmax, mode)
     want = az.encode_frames(rows, params, n, tail, n_tail, sample_bits=bits, channels=C, sample_size=ss,
                             first_frame=first)
