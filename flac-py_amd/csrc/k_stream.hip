@@ -30,7 +30,8 @@
  *     sits between barriers;
  *   - the chosen residual is written to HBM from registers and kept as packed 16-bit pairs;
  *     Rice data bits on those pairs (v_pk_lshrrev_b16 + v_dot2_u32_u16) when a chunk's
- *     values are < 2^16;
+ *     values are < 2^16, summed once per distinct parameter of a wave's chunk slot (nested
+ *     partitions mostly share floor(log2(mean)));
  *   - the 208-byte meta record is one coalesced store of 52 lanes.
  */
 #include <type_traits>
@@ -50,6 +51,13 @@ typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 #define FLACMI_STREAM_CPT 5
 #endif
 constexpr int kSCPT = FLACMI_STREAM_CPT; /* max 8-sample chunks per thread */
+/* A/B builds (timing only, same results): 0 takes the earlier code */
+#ifndef FLACMI_RICE_DEDUP
+#define FLACMI_RICE_DEDUP 1 /* Rice data bits once per distinct parameter of a wave's chunk slot */
+#endif
+#ifndef FLACMI_SAD16
+#define FLACMI_SAD16 1 /* staging's sum|x| on v_sad_u16 */
+#endif
 /* workgroup size: 8-sample chunks, up to kSCPT per thread */
 __host__ __device__ constexpr int stream_threads(int n) {
     const int nch = n / 8;
@@ -388,7 +396,11 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         }
         if (tid < kSHP) xs[tid - kSHP] = 0x8000u; /* biased zeros */
         if (tid < Pmax) pks[tid] = a.stop_after == 10 ? (uint32_t)n * 40u : 0u; /* 10: no atomics, sums nonzero */
+#if FLACMI_SAD16
+        const uint32_t k8000 = opaque(0x80008000u); /* biased zero in both halves */
+#else
         const uint32_t k8000 = opaque(0x8000u);
+#endif
         uint32_t sumx = 0;
 #pragma unroll
         for (int j = 0; j < kSCPT; ++j) {
@@ -399,8 +411,14 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                 const uint32_t yd[4] = {y.x, y.y, y.z, y.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
+#if FLACMI_SAD16
+                    /* one v_sad_u16 per dword: |lo - 0x8000| + |hi - 0x8000| + sumx (per lane at
+                     * most 8 kSCPT samples of 2^15: far below 2^32) */
+                    sumx = __builtin_amdgcn_sad_u16(yd[e], k8000, sumx);
+#else
                     sumx = sad32(yd[e] & 0xffffu, k8000, sumx);
                     sumx = sad32(yd[e] >> 16, k8000, sumx);
+#endif
                 }
             }
         }
@@ -938,6 +956,79 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
     uint32_t tb[kRiceOrders];
 #pragma unroll
     for (int o2 = 0; o2 < kRiceOrders; ++o2) tb[o2] = 0;
+#if FLACMI_RICE_DEDUP
+    /* An order's parameter on a chunk is its ancestor partition's floor(log2(mean)), and nested
+     * partitions mostly share it: the sum of z >> p is computed once per distinct parameter of
+     * the wave's chunk slot.  Two orders count as equal only when they agree on every voting
+     * lane (active, chunk on the packed path), so every decision is wave-uniform and the
+     * result is the same for any input.  tc: the sums of the slots where every order agrees,
+     * added to every order's total after the loop. */
+    uint32_t tc = 0;
+#pragma unroll
+    for (int jc = 0; jc < kSCPT; ++jc) {
+        const int c = tid + jc * NT;
+        if (c < nch) {
+            const int k = part_of(c);
+            uint32_t pw[kRiceOrders / 2];
+            load_ptab(pkw + k * RS, pw);
+            big |= ((pw[0] >> 15) & 1u) << jc; /* a parameter >= 16 in this chunk's row */
+            const bool vote = !((big >> jc) & 1);
+            /* dd[w]: order 2w against 2w - 1 (low half) and 2w + 1 against 2w (high half), entry
+             * 0 without its flag; mk: the halves of the orders ro + 1 .. oo */
+            uint32_t prev = 0, alld = 0;
+            uint32_t dd[kRiceOrders / 2];
+#pragma unroll
+            for (int w = 0; w < kRiceOrders / 2; ++w) {
+                const uint32_t cur = w == 0 ? pw[0] & 0xffff7fffu : pw[w];
+                const uint32_t mk = ((2 * w > ro && 2 * w <= oo) ? 0x0000ffffu : 0u) |
+                                    ((2 * w + 1 > ro && 2 * w + 1 <= oo) ? 0xffff0000u : 0u);
+                dd[w] = (cur ^ __builtin_amdgcn_alignbit(cur, prev, 16)) & mk;
+                alld |= dd[w];
+                prev = cur;
+            }
+            if (__ballot(vote && alld != 0) == 0) {
+                /* every order shifts by the same parameter on every voting lane: order oo's */
+                uint32_t ws = pw[0];
+#pragma unroll
+                for (int w = 1; w < kRiceOrders / 2; ++w) ws = (oo >> 1) == w ? pw[w] : ws;
+                if (vote) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const uint32_t sh = (oo & 1) ? pk_shr_bcast<1>(ws, zp[jc][i]) : pk_shr_bcast<0>(ws, zp[jc][i]);
+                        tc = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, sh), us2{1, 1}, tc, false);
+                    }
+                }
+            } else {
+                /* walk the orders: bit o2 of fresh = order o2 differs from o2 - 1 on some voting
+                 * lane (or is the first), else it takes the previous order's chunk sum */
+                uint32_t fresh = 1u << ro;
+#pragma unroll
+                for (int o2 = 1; o2 < kRiceOrders; ++o2)
+                    if (o2 > ro && o2 <= oo) {
+                        const uint32_t h = (o2 & 1) ? dd[o2 >> 1] >> 16 : dd[o2 >> 1] & 0xffffu;
+                        fresh |= __ballot(vote && h != 0) != 0 ? 1u << o2 : 0u;
+                    }
+                if (vote) {
+                    uint32_t cs = 0;
+#pragma unroll
+                    for (int o2 = 0; o2 < kRiceOrders; ++o2)
+                        if (o2 >= ro && o2 <= oo) {
+                            if ((fresh >> o2) & 1) {
+                                cs = 0;
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) {
+                                    const uint32_t sh = (o2 & 1) ? pk_shr_bcast<1>(pw[o2 >> 1], zp[jc][i])
+                                                                 : pk_shr_bcast<0>(pw[o2 >> 1], zp[jc][i]);
+                                    cs = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, sh), us2{1, 1}, cs, false);
+                                }
+                            }
+                            tb[o2] += cs;
+                        }
+                }
+            }
+        }
+    }
+#else
 #pragma unroll
     for (int jc = 0; jc < kSCPT; ++jc) {
         const int c = tid + jc * NT;
@@ -960,6 +1051,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
             }
         }
     }
+#endif
     /* rare: chunks holding a value >= 2^16 recompute their residual, in one loop that is not
      * unrolled (one inlined copy of the six predictors instead of one per chunk slot: the
      * kernel's code, and its instruction-cache footprint, shrink by a third) */
@@ -983,6 +1075,12 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         }
     }
     {
+#if FLACMI_RICE_DEDUP
+        /* the common sums belong to every order's total (before the 2^26 test below) */
+#pragma unroll
+        for (int o2 = 0; o2 < kRiceOrders; ++o2)
+            if (o2 >= ro && o2 <= oo) tb[o2] += tc;
+#endif
         uint32_t any = 0;
 #pragma unroll
         for (int o2 = 0; o2 < kRiceOrders; ++o2) any |= (o2 >= ro && o2 <= oo) ? tb[o2] : 0u;
