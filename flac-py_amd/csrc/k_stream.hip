@@ -802,9 +802,13 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         for (int o = a.rmin; o <= a.rmax; ++o)
             if ((n % (1 << o)) == 0 && (n >> o) > order) omax = o;
     const int P = 1 << (omax < 0 ? 0 : omax), cpp = (n >> (omax < 0 ? 0 : omax)) >> 3;
-    /* finest partition of chunk c = floor(c / cpp) = mulhi(c, ceil(2^32 / cpp)): exact for c * cpp < 2^32 */
+    /* finest partition of chunk c = floor(c / cpp) = mulhi(c, ceil(2^32 / cpp)): exact for c * cpp < 2^32.
+     * cpp == 1 (8-sample finest partitions, e.g. n = 256 with orders 0..5) is taken apart: 2^32 does
+     * not fit the 32-bit multiplier (it would wrap to 0 and send every chunk to partition 0) */
     const uint32_t mcpp = (uint32_t)((0x100000000ull + (uint64_t)cpp - 1) / (uint64_t)cpp);
-    auto part_of = [&](int c) __attribute__((always_inline)) -> int { return (int)__umulhi((uint32_t)c, mcpp); };
+    auto part_of = [&](int c) __attribute__((always_inline)) -> int {
+        return cpp == 1 ? c : (int)__umulhi((uint32_t)c, mcpp);
+    };
     uint32_t* __restrict__ rout = reinterpret_cast<uint32_t*>(a.residual) + gid * a.residual_stride;
     const int fixed_k = __builtin_amdgcn_readfirstlane(lpc_wins ? -1 : order);
     const int lsh = mv.shift;
