@@ -330,7 +330,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
 static int get_window(flacmi_ctx* ctx, int n, double** out, int* one_lo = nullptr, int* one_hi = nullptr) {
     auto it = ctx->windows.find(n);
     if (it == ctx->windows.end()) {
-        std::vector<double> w = tukey_window(n, 64);
+        std::vector<double> w = tukey_window(n, kWindowPad);
         double* d = nullptr;
         HIP_TRY(hipMalloc(&d, sizeof(double) * w.size()));
         HIP_TRY(hipMemcpy(d, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));

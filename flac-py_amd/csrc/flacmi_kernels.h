@@ -10,6 +10,13 @@
 
 namespace flacmi {
 
+/* Zero entries behind the n weights of a unit's Tukey window (get_window).  The k_lpc kernels
+ * read the window for every slot of their last load block / ring cycle / tile, whose samples
+ * at and past n - 1 are loaded as 0: up to one whole block (k_lpc: SB, k_lpc_tile: 64) past
+ * n - 1.  At least the largest SB of any build (80: 16-bit samples at LMAX 32); each kernel
+ * asserts its own block against it. */
+constexpr int kWindowPad = 80;
+
 /* One launch = one "length class": units [unit0, unit0 + count) that all have length n. */
 struct LpcArgs {
     const void* samples;     /* batch base pointer */

@@ -184,6 +184,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lpc_waves(L
     constexpr int PK = sizeof(SampleT) == 2 ? 2 : 1; /* samples per 32-bit word */
     constexpr int SB = sizeof(SampleT) == 2 ? 2 * S : S;
     constexpr int W = SB / PK;
+    static_assert(SB <= kWindowPad, "the last block's window reads stay inside the window's zero pad");
     const int nblk = (M + SB - 1) / SB;
     uint32_t cur[W];
     auto load = [&](int m0, uint32_t (&v)[W]) __attribute__((always_inline)) {
@@ -369,6 +370,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LMAX <= 12 
     int32_t* __restrict__ rec = a.rec + gid * a.rec_words;
     constexpr int S = ((LMAX + 1 + 7) / 8) * 8;
     static_assert(32 % S == 0, "ring length divides a half tile");
+    static_assert(64 <= kWindowPad, "the last tile's window reads stay inside the window's zero pad");
     double acc[LMAX + 1];
     if (n >= 4 && n <= 7) { /* tukey: nr == 0 -> pi * 0 / 0 (encoder.py:437) */
         rec[0] = ST_ZERODIV | (FLACMI_SITE_TUKEY << 16);

@@ -311,6 +311,20 @@ def edge_set():
     return E_
 
 
+def lpc_shapes_set():
+    """The block lengths of tests/lpc_shape_cases.py (short, odd, off every tile / ring-cycle /
+    load-block multiple of the k_lpc kernels) on the reference itself: two synthetic units per
+    row, one per L = 32 row (the fixture stays smaller than edge.json)."""
+    rows = [(n, 16, 12, 5, range(0, 6), 2) for n in (3, 5, 9, 66, 100, 193, 322, 882, 2049, 4410)]
+    rows += [(n, 16, 32, 12, range(0, 6), 1) for n in (8, 82, 322, 882)]
+    rows += [(n, 24, 32, 15, range(0, 9), 1) for n in (42, 322, 882, 4410)]
+    rows += [(322, 24, 8, 12, range(0, 6), 2)]
+    E_ = []
+    for n, bits, L, q, rr, k in rows:
+        E_ += synth_set(f"lpc_shapes n={n} bits={bits} L={L}", range(k), n, bits, 7000 + n + L, L, q, rr)
+    return E_
+
+
 def stream_set():
     """Whole-stream fixtures: reference encode() bytes (and its CLI) for config 1."""
     from flac.encoder import EncoderParameters, encode
@@ -500,6 +514,9 @@ def main(which):
                                             fixed_only=True)})
     if "edge" in which:
         dump("edge.json", {"config": "edge cases and reference exceptions", "units": edge_set()})
+    if "lpc_shapes" in which:
+        dump("lpc_shapes.json", {"config": "k_lpc block lengths: short, odd, off the tile / ring / block sizes",
+                                 "units": lpc_shapes_set()})
     if "stream" in which:
         dump("streams.json", stream_set())
     if "bursts" in which:
@@ -510,4 +527,4 @@ def main(which):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or ["c2", "c1", "c3", "c5", "edge", "stream", "acf"])
+    main(sys.argv[1:] or ["c2", "c1", "c3", "c5", "edge", "lpc_shapes", "stream", "acf"])

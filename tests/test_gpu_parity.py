@@ -39,7 +39,7 @@ def run_units(az, units, n, params, bits=16, tail=None, debug=True, residual_byt
 # golden fixtures (produced by the reference itself)
 # ---------------------------------------------------------------------------------------
 def _golden_cases():
-    for s in ["c1.json", "c2.json", "c3.json", "c5.json", "edge.json"]:
+    for s in ["c1.json", "c2.json", "c3.json", "c5.json", "edge.json", "lpc_shapes.json"]:
         d = G.load(s)
         for i, e in enumerate(d["units"]):
             tag = e["source"].get("tag") or f"u{e['source'].get('unit', i)}"

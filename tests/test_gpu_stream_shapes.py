@@ -8,8 +8,10 @@ tests/stream_shape_cases.py (tests/test_stream_shape_cases.py runs those without
 
 Which kernel took a unit is read off meta.lpc_tiers in reference mode (x/4: the batch kernel's
 quarter tiers, 1/1: its list kernel, 0/1 or 1/1 after the sign bound: k_resid's list variant);
-the debug call also pins acf, every fixed and LPC sum and the LPC records, which sweeps
-k_lpc_tile<4/8/12> over the same lengths."""
+the debug call also pins acf, every fixed and LPC sum and the LPC records.  Only the 68-unit cases
+(orders 0..5: n = 256, 2560, 2816, 4096, 5120, 5376, 7680, 7936, 10240) reach k_lpc_tile<4/8/12>
+with them: the others hold 56 or 62 units, fewer than the tile kernel's whole wave of 64, and run
+k_lpc<LMAX,int16_t>.  tests/test_gpu_lpc_shapes.py sweeps the k_lpc kernels over block lengths."""
 import numpy as np
 import pytest
 

@@ -9,7 +9,7 @@ import pytest
 import golden_util as G
 import oracle
 
-SETS = ["c1.json", "c2.json", "c3.json", "c5.json", "edge.json"]
+SETS = ["c1.json", "c2.json", "c3.json", "c5.json", "edge.json", "lpc_shapes.json"]
 
 
 def _cases():
