@@ -191,7 +191,82 @@ DSITE = {name: 32 + i for i, name in enumerate((
     "sync", "block_size_code", "sample_rate_code", "channels_code", "sample_size_code", "reserved",
     "subframe_pad", "subframe_type", "lpc_precision", "coding_method", "partitions", "escape_zero",
     "neg_shift", "padding", "eof", "crc8", "crc16", "frame_end", "frame_number", "block_size", "channels",
-    "samples"))}
+    "samples", "pcm_range"))}
+DSITE_NAMES = {v: k for k, v in DSITE.items()}
+
+
+class FrameCandidate(C.Structure):
+    _fields_ = [
+        ("offset", C.c_int64),
+        ("coded_number", C.c_int64),
+        ("block_size", C.c_int32),
+        ("header_bytes", C.c_int32),
+        ("channel_code", C.c_int32),
+        ("sample_size_code", C.c_int32),
+    ]
+
+
+# numpy view of flacmi_frame_candidate
+CANDIDATE_DTYPE = np.dtype([("offset", "<i8"), ("coded_number", "<i8"), ("block_size", "<i4"),
+                            ("header_bytes", "<i4"), ("channel_code", "<i4"), ("sample_size_code", "<i4")])
+assert CANDIDATE_DTYPE.itemsize == C.sizeof(FrameCandidate) == 32
+
+
+class PcmFrame(C.Structure):
+    _fields_ = [
+        ("rows", C.c_void_p),
+        ("stride", C.c_int64),
+        ("first_sample", C.c_int64),
+        ("block_size", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+PCM_FRAME_DTYPE = np.dtype([("rows", "<u8"), ("stride", "<i8"), ("first_sample", "<i8"), ("block_size", "<i4"),
+                            ("reserved0", "<i4")])
+assert PCM_FRAME_DTYPE.itemsize == C.sizeof(PcmFrame) == 32
+PCM_PACKED, PCM_RAW32 = 0, 1  # flacmi_pcm_mode
+
+# flacmi_walk_state
+WALK_RUN, WALK_DONE, WALK_STOPPED, WALK_PROBE, WALK_FULL = 0, 1, 2, 3, 4
+
+
+class ChainFrame(C.Structure):
+    _fields_ = [
+        ("offset", C.c_int64),
+        ("end", C.c_int64),
+        ("candidate", C.c_int64),
+        ("status", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class Walk(C.Structure):
+    _fields_ = [
+        ("pos", C.c_int64),
+        ("n_chain", C.c_int64),
+        ("state", C.c_int32),
+        ("stop_status", C.c_int32),
+        ("probe_status", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("probe_end", C.c_int64),
+    ]
+
+
+class StreamResult(C.Structure):
+    _fields_ = [
+        ("frames", C.c_int64),
+        ("samples", C.c_int64),
+        ("pcm_bytes", C.c_int64),
+        ("consumed", C.c_int64),
+        ("status", C.c_int32),
+        ("site", C.c_int32),
+        ("candidates", C.c_int64),
+        ("probes", C.c_int64),
+        ("pass2_frames", C.c_int64),
+        ("pcm_full", C.c_int64),
+        ("reserved0", C.c_int64),
+    ]
 
 
 COMM_ID_BYTES = 128  # FLACMI_COMM_ID_BYTES
@@ -225,6 +300,19 @@ SIGNATURES = {
     "flacmi_decode_frames_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                               C.POINTER(DecodeParams), C.POINTER(Batch), C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flacmi_decode_frames_end_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                  C.POINTER(DecodeParams), C.POINTER(Batch), C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flacmi_index_tile_bytes": (C.c_int32, []),
+    "flacmi_index_frames_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_void_p]),
+    "flacmi_pcm_out_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "flacmi_host_chain_walk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.POINTER(Walk), C.c_void_p, C.c_int64]),
+    "flacmi_decode_stream_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DecodeParams),
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                            C.POINTER(StreamResult)]),
     "flacmi_stream_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_void_p, C.c_void_p]),
     "flacmi_comm_available": (C.c_int, []),

@@ -370,6 +370,73 @@ class Analyzer:
         torch.cuda.synchronize(dev)
         return out.cpu().numpy(), st.cpu().numpy()[:n_frames], mm.cpu().numpy()[:n_frames]
 
+    def index_frames(self, data, first_byte: int = 0, capacity: int = 0, base_offset: int = 0):
+        """Host bytes in -> (candidate table as a CANDIDATE_DTYPE array, the true count), from
+        the device frame index.  capacity 0: retried until the table holds every candidate.
+        base_offset (a multiple of 4): the stream starts that many bytes into its device
+        buffer, so its base is not 16-byte aligned."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        nb = int(len(data))
+        assert base_offset % 4 == 0
+        buf = torch.full((base_offset + ((nb + 3) // 4) * 4 + 16,), 0xFF, dtype=torch.uint8, device=dev)
+        if nb:
+            buf[base_offset:base_offset + nb] = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cap = capacity if capacity > 0 else max(64, nb // 512)
+        while True:
+            table = torch.zeros((max(cap, 1), abi.CANDIDATE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            check(self.lib.flacmi_index_frames_device(self.ctx, buf.data_ptr() + base_offset, nb, first_byte, table.data_ptr(), cap,
+                                                      count.data_ptr(), stream), "flacmi_index_frames_device")
+            torch.cuda.synchronize(dev)
+            n = int(count.item())
+            if n <= cap or capacity > 0:
+                break
+            cap = n
+        return table.cpu().numpy().view(abi.CANDIDATE_DTYPE).reshape(-1)[:min(n, cap)].copy(), n
+
+    def pcm_out(self, rows: np.ndarray, block_sizes, channels: int, bytes_per_sample: int, raw: bool = False,
+                lead_bytes: int = 0):
+        """int32 rows [n_frames*channels][stride] and the frames' block sizes -> (interleaved PCM
+        bytes, status per frame, total bytes) from the device PCM writer.  The frames follow each
+        other; the first starts at byte lead_bytes (a multiple of channels * B), so a test
+        chooses the alignment of every frame's first byte."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B = 4 if raw else bytes_per_sample
+        assert lead_bytes % (channels * B) == 0
+        r = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
+        stride = r.shape[1]
+        t = np.zeros(len(block_sizes), dtype=abi.PCM_FRAME_DTYPE)
+        first = lead_bytes // (channels * B)
+        for f, bs in enumerate(block_sizes):
+            t[f] = (r.data_ptr() + 4 * f * channels * stride, stride, first, bs, 0)
+            first += bs
+        total = first * channels * B
+        tab = torch.from_numpy(t.view(np.uint8)).to(dev)
+        out = torch.full((((total + 3) // 4) * 4 + 16,), 0xA5, dtype=torch.uint8, device=dev)
+        st = torch.zeros(max(len(block_sizes), 1), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self.lib.flacmi_pcm_out_device(self.ctx, tab.data_ptr(), len(block_sizes), channels, bytes_per_sample,
+                                             abi.PCM_RAW32 if raw else abi.PCM_PACKED, out.data_ptr(), total,
+                                             st.data_ptr(), stream), "flacmi_pcm_out_device")
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy(), st.cpu().numpy()[:len(block_sizes)], total
+
+    def decode_stream(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
+                      check_crc: bool, max_block_size: int, final_chunk: bool, pcm_ptr: int, pcm_capacity: int,
+                      raw: bool, bytes_per_sample: int) -> abi.StreamResult:
+        """flacmi_decode_stream_host: one chunk of host stream bytes -> host PCM."""
+        dp = abi.DecodeParams()
+        dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, int(check_crc)
+        res = abi.StreamResult()
+        check(self.lib.flacmi_decode_stream_host(self.ctx, data_ptr, nbytes, first_byte, C.byref(dp), max_block_size,
+                                                 int(final_chunk), pcm_ptr, pcm_capacity,
+                                                 abi.PCM_RAW32 if raw else abi.PCM_PACKED, bytes_per_sample,
+                                                 C.byref(res)), "flacmi_decode_stream_host")
+        return res
+
     def timing(self) -> dict:
         """Average k_lpc / k_resid / whole-call milliseconds over the analyze calls since
         the last timing_reset() (HIP events recorded on each call's stream)."""

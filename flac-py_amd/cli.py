@@ -1,5 +1,5 @@
-"""Command line with flac/__main__.py's `encode` action (its arguments, defaults and
-output bytes), on the device path: streamed PCM ingest (ingest.iter_wav_pcm, the
+"""Command line with flac/__main__.py's `encode` and `decode` actions (their arguments,
+defaults and output bytes), on the device path.  encode: streamed PCM ingest (ingest.iter_wav_pcm, the
 reference reader's byte grouping unless --correct-reader), device analysis and device
 frame writer through the streaming pipeline (encoder.encode_wav); --devices spreads the
 batches over several GPUs.
@@ -8,8 +8,12 @@ batches over several GPUs.
                                                        [--correct-reader] [--fixed-only]
                                                        [--device N | --devices N,M,...]
 
-The reference's `decode` action (a WAV writer over its host decoder) is not part of this
-build; the device decoder (flacmi_decode_frames_device) is a frame verifier.
+    python -m flac_amd decode infile.flac outfile.wav [--device N] [--check-crc]
+
+decode (__main__.py:27-55 cmd_decode): the stream's frames are found, decoded, interleaved and
+packed on the device (decoder.decode_wav over flacmi_decode_stream_host) and written through
+the wave module as the reference does; --check-crc also verifies CRC-8 / CRC-16, which the
+reference reads unchecked.
 """
 import argparse
 import sys
@@ -41,7 +45,19 @@ def make_argument_parser():
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
+    dec = action.add_parser("decode", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    dec.add_argument("infile", type=Path, metavar="infile.flac")
+    dec.add_argument("outfile", type=Path, metavar="outfile.wav")
+    dec.add_argument("--device", type=int, default=0)
+    dec.add_argument("--check-crc", action="store_true",
+                     help="verify the frames' CRC-8 and CRC-16 (the reference reads them unchecked)")
     return parser
+
+
+def cmd_decode(args) -> None:
+    from .decoder import decode_wav
+    seconds = decode_wav(args.infile, args.outfile, device=args.device, check_crc=args.check_crc)
+    print(f"Decoding completed in {seconds:.6g} seconds")
 
 
 def cmd_encode(args) -> None:
@@ -61,6 +77,8 @@ def main(argv=None) -> int:
     args = make_argument_parser().parse_args(argv)
     if args.action == "encode":
         cmd_encode(args)
+    if args.action == "decode":
+        cmd_decode(args)
     return 0
 
 

@@ -164,6 +164,7 @@ struct flacmi_ctx {
     DevBuf rec, retry, h_samples, h_meta, h_params, h_residual, h_acf, h_fs, h_ls, h_recs;
     uint16_t* d_crc = nullptr;  /* CRC-16 slice tables [4][256] + power tables [28][512] */
     DevBuf scan, h_offsets, h_status, h_frames, dec, slow;
+    DevBuf idx, sd_data, sd_table, sd_meta, sd_rows, sd_pcm; /* frame index workspace; flacmi_decode_stream_host's buffers */
     int64_t frames_bytes = 0;   /* bytes of the last flacmi_encode_host call */
     static constexpr int kRing = 64;
     static constexpr int kMaxChunks = 8;
@@ -309,7 +310,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     (void)hipDeviceSynchronize();
     enc_free(ctx->enc);
     for (auto& kv : ctx->windows) (void)hipFree(kv.second);
-    for (DevBuf* b : {&ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
+    for (DevBuf* b : {&ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
                       &ctx->h_frames})
         if (b->p) (void)hipFree(b->p);
@@ -859,6 +860,31 @@ int flacmi_decode_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int
                                 const flacmi_decode_params* dp, const flacmi_batch* expect,
                                 int32_t* samples_out, int64_t out_stride, int32_t* frame_status,
                                 int64_t* frame_mismatch, void* stream) {
+    return flacmi_decode_frames_end_device(ctx, stream_data, stream_bytes, frame_offsets, n_frames, dp, expect,
+                                           samples_out, out_stride, frame_status, frame_mismatch, nullptr, stream);
+}
+
+static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                              const int64_t* frame_offsets, int64_t n_frames, const flacmi_decode_params* dp,
+                              const flacmi_batch* expect, int32_t* samples_out, int64_t out_stride,
+                              int32_t* frame_status, int64_t* frame_mismatch, int64_t* frame_end, bool general,
+                              void* stream);
+
+int flacmi_decode_frames_end_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                                    const int64_t* frame_offsets, int64_t n_frames,
+                                    const flacmi_decode_params* dp, const flacmi_batch* expect,
+                                    int32_t* samples_out, int64_t out_stride, int32_t* frame_status,
+                                    int64_t* frame_mismatch, int64_t* frame_end, void* stream) {
+    return decode_frames_impl(ctx, stream_data, stream_bytes, frame_offsets, n_frames, dp, expect, samples_out,
+                              out_stride, frame_status, frame_mismatch, frame_end, false, stream);
+}
+
+/* general: every frame through the general decoder kernel, as knob FLACMI_DECODE_GENERIC */
+static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                              const int64_t* frame_offsets, int64_t n_frames, const flacmi_decode_params* dp,
+                              const flacmi_batch* expect, int32_t* samples_out, int64_t out_stride,
+                              int32_t* frame_status, int64_t* frame_mismatch, int64_t* frame_end, bool general,
+                              void* stream) {
     if (!ctx || !dp) return fail(FLACMI_E_INVALID, "null argument");
     if (n_frames < 0 || stream_bytes < 0) return fail(FLACMI_E_INVALID, "negative size");
     if (n_frames == 0) return 0;
@@ -909,9 +935,403 @@ int flacmi_decode_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int
     a.defer_list = (int64_t*)((char*)ctx->dec.p + dlist + 16);
     a.defer2_count = (unsigned long long*)((char*)ctx->dec.p + dl2);
     a.defer2_list = (int64_t*)((char*)ctx->dec.p + dl2 + 16);
-    a.defer_all = knob(kKnobDecodeGeneric) != 0;
+    a.defer_all = general || knob(kKnobDecodeGeneric) != 0;
     a.crc_slice = ctx->d_crc;
+    a.frame_end = frame_end;
     HIP_TRY(launch_decode(a, (hipStream_t)stream));
+    return 0;
+}
+
+/* ---- stream decoder ------------------------------------------------------------------ */
+int32_t flacmi_index_tile_bytes(void) { return kIndexTile; }
+
+int flacmi_index_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                               int64_t first_byte, flacmi_frame_candidate* table, int64_t capacity,
+                               int64_t* count, void* stream) {
+    if (!ctx || !count) return fail(FLACMI_E_INVALID, "null argument");
+    if (stream_bytes < 0 || first_byte < 0 || capacity < 0) return fail(FLACMI_E_INVALID, "negative size");
+    if (stream_bytes > 0 && !stream_data) return fail(FLACMI_E_INVALID, "null buffer");
+    if (capacity > 0 && !table) return fail(FLACMI_E_INVALID, "null table");
+    if (((uintptr_t)stream_data & 3) != 0) return fail(FLACMI_E_INVALID, "stream_data must be 4-byte aligned");
+    if (((uintptr_t)table & 7) != 0 || ((uintptr_t)count & 7) != 0)
+        return fail(FLACMI_E_INVALID, "table and count must be 8-byte aligned");
+    if (int rc = set_device(ctx)) return rc;
+    IndexArgs a{};
+    a.base = stream_data;
+    a.bytes = stream_bytes;
+    a.first = first_byte;
+    a.mis = (int32_t)((uintptr_t)stream_data & 15);
+    a.n_tiles = stream_bytes > 0 ? (a.mis + stream_bytes + kIndexTile - 1) / kIndexTile : 0;
+    if (a.n_tiles > 0x7FFFFFFF) return fail(FLACMI_E_UNSUPPORTED, "stream of %lld bytes: index it in parts", (long long)stream_bytes);
+    a.table = table;
+    a.capacity = capacity;
+    a.count = count;
+    /* workspace: group bases i64, then tile bases [n_tiles] i32 and tile counts [n_tiles + 3] i32 */
+    const size_t ng = (size_t)index_scan_groups(a.n_tiles);
+    if (int rc = ensure_buf(ctx->idx, 8 * ng + 8 * (size_t)a.n_tiles + 32)) return rc;
+    a.group_base = (int64_t*)ctx->idx.p;
+    a.tile_base = (int32_t*)((char*)ctx->idx.p + 8 * ng);
+    a.tile_count = a.tile_base + a.n_tiles;
+    HIP_TRY(launch_index(a, (hipStream_t)stream));
+    return 0;
+}
+
+int flacmi_pcm_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64_t n_frames, int32_t channels,
+                          int32_t bytes_per_sample, int32_t mode, uint8_t* out, int64_t out_capacity,
+                          int32_t* frame_status, void* stream) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null argument");
+    if (n_frames < 0 || out_capacity < 0) return fail(FLACMI_E_INVALID, "negative size");
+    if (channels < 1 || channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (mode != FLACMI_PCM_PACKED && mode != FLACMI_PCM_RAW32) return fail(FLACMI_E_INVALID, "mode must be a flacmi_pcm_mode");
+    if (mode == FLACMI_PCM_PACKED && (bytes_per_sample < 1 || bytes_per_sample > 4))
+        return fail(FLACMI_E_INVALID, "bytes_per_sample must be 1..4");
+    if (n_frames == 0) return 0;
+    if (!frames || !out || !frame_status) return fail(FLACMI_E_INVALID, "null buffer");
+    if (((uintptr_t)out & 3) != 0 || ((uintptr_t)frames & 7) != 0) return fail(FLACMI_E_INVALID, "out must be 4-byte aligned");
+    if (n_frames > 0x7FFFFFFF) return fail(FLACMI_E_UNSUPPORTED, "more than 2^31 - 1 frames in one call");
+    if (int rc = set_device(ctx)) return rc;
+    PcmArgs a{};
+    a.frames = frames;
+    a.n_frames = n_frames;
+    a.channels = channels;
+    a.bytes_per_sample = mode == FLACMI_PCM_RAW32 ? 4 : bytes_per_sample;
+    a.raw = mode == FLACMI_PCM_RAW32;
+    a.out = out;
+    a.capacity = out_capacity;
+    a.status = frame_status;
+    HIP_TRY(launch_pcm(a, (hipStream_t)stream));
+    return 0;
+}
+
+static inline bool walk_ref_error(int32_t st) { return st != 0 && (st & 0xFFFF) != FLACMI_STATUS_VERIFY; }
+
+int flacmi_host_chain_walk(const flacmi_frame_candidate* table, int64_t n_candidates, const int32_t* status,
+                           const int64_t* frame_end, int64_t stream_bytes, int32_t final_chunk, flacmi_walk* w,
+                           flacmi_chain_frame* chain, int64_t chain_capacity) {
+    (void)final_chunk; /* an EOFError frame leaves w->pos at its start either way: the final chunk's caller ends
+                          the stream there, any other caller carries the tail over */
+    if (!w || n_candidates < 0 || stream_bytes < 0 || chain_capacity < 0) return fail(FLACMI_E_INVALID, "bad argument");
+    if (n_candidates > 0 && (!table || !status || !frame_end)) return fail(FLACMI_E_INVALID, "null table");
+    if (chain_capacity > 0 && !chain) return fail(FLACMI_E_INVALID, "null chain");
+    if (w->pos < 0 || w->n_chain < 0 || w->n_chain > chain_capacity) return fail(FLACMI_E_INVALID, "bad walk state");
+    if (w->state == FLACMI_WALK_DONE || w->state == FLACMI_WALK_STOPPED) return 0;
+    bool probed = w->state == FLACMI_WALK_PROBE;
+    for (;;) {
+        const int64_t pos = w->pos;
+        if (pos >= stream_bytes) {
+            w->state = FLACMI_WALK_DONE;
+            return 0;
+        }
+        /* the candidate at exactly pos */
+        int64_t lo = 0, hi = n_candidates;
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (table[mid].offset < pos) lo = mid + 1;
+            else hi = mid;
+        }
+        const int64_t k = (lo < n_candidates && table[lo].offset == pos) ? lo : -1;
+        int32_t st;
+        int64_t end;
+        const bool was_probed = probed;
+        if (probed) {
+            st = w->probe_status;
+            end = w->probe_end;
+            probed = false;
+            if (!walk_ref_error(st) && end <= pos) { /* not parsed to its end */
+                w->state = FLACMI_WALK_STOPPED;
+                w->stop_status = st ? st : ((FLACMI_DSITE_FRAME_END << 16) | FLACMI_STATUS_VERIFY);
+                return 0;
+            }
+        } else if (k < 0) {
+            w->state = FLACMI_WALK_PROBE;
+            return 0;
+        } else {
+            st = status[k];
+            end = st == 0 ? (k + 1 < n_candidates ? table[k + 1].offset : stream_bytes) : frame_end[k];
+            if (!walk_ref_error(st) && end <= pos) { /* a block larger than the first pass's rows */
+                w->state = FLACMI_WALK_PROBE;
+                return 0;
+            }
+        }
+        if (walk_ref_error(st)) {
+            if ((st & 0xFFFF) == FLACMI_STATUS_EOF) {
+                w->state = FLACMI_WALK_DONE;
+            } else {
+                w->state = FLACMI_WALK_STOPPED;
+                w->stop_status = st;
+            }
+            return 0;
+        }
+        if (w->n_chain >= chain_capacity) {
+            w->state = FLACMI_WALK_FULL;
+            if (was_probed) { /* keep the probe's answer for the next call */
+                w->state = FLACMI_WALK_PROBE;
+                w->probe_status = st;
+                w->probe_end = end;
+                return fail(FLACMI_E_NOMEM, "chain_capacity reached on a probed frame: pass room for one more");
+            }
+            return 0;
+        }
+        flacmi_chain_frame& c = chain[w->n_chain++];
+        c.offset = pos;
+        c.end = end;
+        c.candidate = k;
+        /* a probed frame's rows are the caller's to decode again: never final */
+        c.status = (was_probed && st == 0) ? ((FLACMI_DSITE_FRAME_END << 16) | FLACMI_STATUS_VERIFY) : st;
+        c.reserved0 = 0;
+        w->pos = end;
+        w->state = FLACMI_WALK_RUN;
+    }
+}
+
+namespace {
+struct ScopedDev { /* device scratch of one flacmi_decode_stream_host call */
+    void* p = nullptr;
+    ~ScopedDev() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t bytes) {
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
+            p = nullptr;
+            return fail(FLACMI_E_NOMEM, "hipMalloc of %zu bytes failed", bytes);
+        }
+        return 0;
+    }
+};
+}  // namespace
+
+int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                              const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
+                              uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
+                              flacmi_stream_result* res) {
+    if (!ctx || !dp || !res) return fail(FLACMI_E_INVALID, "null argument");
+    if (bytes < 0 || first_byte < 0 || first_byte > bytes || pcm_capacity < 0) return fail(FLACMI_E_INVALID, "bad size");
+    if (bytes > 0 && !data) return fail(FLACMI_E_INVALID, "null buffer");
+    if (pcm_capacity > 0 && !pcm) return fail(FLACMI_E_INVALID, "null pcm buffer");
+    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (max_block_size < 0 || max_block_size > FLACMI_MAX_BLOCK + 1) return fail(FLACMI_E_INVALID, "max_block_size must be 0..65536");
+    if (mode != FLACMI_PCM_PACKED && mode != FLACMI_PCM_RAW32) return fail(FLACMI_E_INVALID, "mode must be a flacmi_pcm_mode");
+    if (mode == FLACMI_PCM_PACKED && (bytes_per_sample < 1 || bytes_per_sample > 4))
+        return fail(FLACMI_E_INVALID, "bytes_per_sample must be 1..4");
+    memset(res, 0, sizeof(*res));
+    res->consumed = first_byte;
+    if (bytes == first_byte) return 0;
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int ch = dp->channels;
+    const int B = mode == FLACMI_PCM_RAW32 ? 4 : bytes_per_sample;
+    flacmi_decode_params p1 = *dp;
+    p1.first_frame = -1;
+
+    /* 1. the chunk, 2. the index */
+    if (int rc = ensure_buf(ctx->sd_data, (size_t)bytes + 32)) return rc;
+    uint8_t* d_data = (uint8_t*)ctx->sd_data.p;
+    HIP_TRY(hipMemcpyAsync(d_data, data, (size_t)bytes, hipMemcpyHostToDevice, s));
+    int64_t cap = bytes / 512 + 1024, n = 0;
+    for (;;) {
+        if (int rc = ensure_buf(ctx->sd_table, sizeof(flacmi_frame_candidate) * (size_t)cap + 16)) return rc;
+        int64_t* d_count = (int64_t*)ctx->sd_table.p;
+        if (int rc = flacmi_index_frames_device(ctx, d_data, bytes, first_byte,
+                                                (flacmi_frame_candidate*)((char*)ctx->sd_table.p + 16), cap, d_count, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(&n, d_count, sizeof(n), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n <= cap) break;
+        cap = n;
+    }
+    res->candidates = n;
+    std::vector<flacmi_frame_candidate> table((size_t)n);
+    if (n) HIP_TRY(hipMemcpy(table.data(), (char*)ctx->sd_table.p + 16, sizeof(flacmi_frame_candidate) * (size_t)n, hipMemcpyDeviceToHost));
+
+    /* 3. pass 1: every candidate, proposed to end at the next one */
+    int64_t stride1 = max_block_size;
+    if (stride1 == 0)
+        for (const auto& c : table) stride1 = std::max<int64_t>(stride1, c.block_size);
+    stride1 = std::max<int64_t>(4, (stride1 + 3) & ~(int64_t)3);
+    const size_t rows1 = sizeof(int32_t) * (size_t)n * ch * (size_t)stride1;
+    if (rows1 > ((size_t)4 << 30))
+        return fail(FLACMI_E_UNSUPPORTED, "%lld candidates of %lld-sample rows exceed 4 GiB: pass a smaller chunk", (long long)n, (long long)stride1);
+    std::vector<int32_t> st1((size_t)n);
+    std::vector<int64_t> end1((size_t)n);
+    /* per-frame words: offsets [n + 1] i64, ends [n] i64, mismatches [n] i64, status [n] i32 */
+    if (int rc = ensure_buf(ctx->sd_meta, 28 * (size_t)n + 64)) return rc;
+    int64_t* d_off = (int64_t*)ctx->sd_meta.p;
+    int64_t* d_end = d_off + n + 1;
+    int64_t* d_mm = d_end + n;
+    int32_t* d_st = (int32_t*)(d_mm + n);
+    if (n) {
+        std::vector<int64_t> off((size_t)n + 1);
+        for (int64_t k = 0; k < n; ++k) off[k] = table[k].offset;
+        off[n] = bytes;
+        if (int rc = ensure_buf(ctx->sd_rows, rows1)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        if (int rc = flacmi_decode_frames_end_device(ctx, d_data, bytes, d_off, n, &p1, nullptr, (int32_t*)ctx->sd_rows.p, stride1,
+                                                     d_st, d_mm, d_end, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(st1.data(), d_st, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(end1.data(), d_end, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+
+    /* 4. the walk; a probe decodes the one frame at w.pos into rows of the largest block */
+    std::vector<flacmi_chain_frame> chain((size_t)n + 16);
+    flacmi_walk w{};
+    w.pos = first_byte;
+    ScopedDev probe_rows, probe_meta;
+    constexpr int64_t kProbeStride = 65536;
+    for (;;) {
+        if (int rc = flacmi_host_chain_walk(table.data(), n, st1.data(), end1.data(), bytes, final_chunk, &w, chain.data(),
+                                            (int64_t)chain.size()))
+            return rc;
+        if (w.state == FLACMI_WALK_FULL) {
+            chain.resize(chain.size() * 2);
+            w.state = FLACMI_WALK_RUN;
+            continue;
+        }
+        if (w.state != FLACMI_WALK_PROBE) break;
+        if ((int64_t)chain.size() == w.n_chain) chain.resize(chain.size() * 2);
+        if (!probe_rows.p) {
+            if (int rc = probe_rows.alloc(sizeof(int32_t) * (size_t)ch * kProbeStride)) return rc;
+            if (int rc = probe_meta.alloc(64)) return rc;
+        }
+        int64_t* q_off = (int64_t*)probe_meta.p; /* offsets [2], end, mismatch, status */
+        const int64_t off2[2] = {w.pos, bytes};
+        HIP_TRY(hipMemcpyAsync(q_off, off2, sizeof(off2), hipMemcpyHostToDevice, s));
+        int32_t k1 = 0;
+        HIP_TRY(hipStreamSynchronize(s)); /* off2 is a stack array */
+        /* FLACMI_DECODE_GENERIC semantics: the general decoder alone */
+        if (int rc = decode_frames_impl(ctx, d_data, bytes, q_off, 1, &p1, nullptr, (int32_t*)probe_rows.p, kProbeStride,
+                                        (int32_t*)(q_off + 4), q_off + 3, q_off + 2, true, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(&k1, q_off + 4, sizeof(k1), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&w.probe_end, q_off + 2, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        w.probe_status = k1;
+        /* the proposed end was the chunk's: ending anywhere before it is no finding yet */
+        if (!walk_ref_error(k1) && (k1 >> 16) == FLACMI_DSITE_FRAME_END) w.probe_status = 0;
+        ++res->probes;
+    }
+    int64_t nc = w.n_chain;
+    int32_t stop = w.state == FLACMI_WALK_STOPPED ? w.stop_status : 0;
+
+    /* block sizes; 5. pass 2: the chain frames whose pass-1 rows are not final, in runs of
+     * neighbours, with the chain's own offsets */
+    std::vector<int32_t> bsz((size_t)nc);
+    std::vector<int64_t> row2((size_t)nc, -1); /* index among the pass-2 frames */
+    int64_t n2 = 0, stride2 = 4;
+    for (int64_t i = 0; i < nc; ++i) {
+        const flacmi_chain_frame& c = chain[i];
+        if (c.candidate >= 0) {
+            bsz[i] = table[c.candidate].block_size;
+        } else {
+            flacmi_frame_candidate h{};
+            if (!parse_header(data, bytes, c.offset, false, h)) return fail(FLACMI_E_INVALID, "internal: chain frame without a header");
+            bsz[i] = h.block_size;
+        }
+        if (c.status != 0) {
+            row2[i] = n2++;
+            stride2 = std::max<int64_t>(stride2, (bsz[i] + 3) & ~3);
+        }
+    }
+    res->pass2_frames = n2;
+    ScopedDev rows2, meta2;
+    if (n2) {
+        if (int rc = rows2.alloc(sizeof(int32_t) * (size_t)n2 * ch * (size_t)stride2)) return rc;
+        if (int rc = meta2.alloc(32 * (size_t)n2 + 64)) return rc;
+        int64_t* e_off = (int64_t*)meta2.p; /* offsets [2 n2] (a run of r frames uses r + 1), mismatch [n2], status [n2] */
+        int64_t* e_mm = e_off + 2 * n2;
+        int32_t* e_st = (int32_t*)(e_mm + n2);
+        std::vector<int64_t> off;
+        std::vector<int32_t> st2((size_t)n2);
+        struct Run { int64_t first2, count, off0; };
+        std::vector<Run> runs;
+        for (int64_t i = 0; i < nc;) {
+            if (row2[i] < 0) { ++i; continue; }
+            int64_t j = i;
+            const int64_t o0 = (int64_t)off.size();
+            while (j < nc && row2[j] >= 0) off.push_back(chain[j++].offset);
+            off.push_back(chain[j - 1].end);
+            runs.push_back({row2[i], j - i, o0});
+            i = j;
+        }
+        /* off holds n2 + (number of runs) <= 2 n2 entries */
+        HIP_TRY(hipMemcpyAsync(e_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (const Run& r : runs) {
+            if (int rc = flacmi_decode_frames_end_device(ctx, d_data, bytes, e_off + r.off0, r.count, &p1, nullptr,
+                                                         (int32_t*)rows2.p + r.first2 * ch * stride2, stride2, e_st + r.first2,
+                                                         e_mm + r.first2, nullptr, s))
+                return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(st2.data(), e_st, sizeof(int32_t) * (size_t)n2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int64_t i = 0; i < nc; ++i) {
+            if (row2[i] >= 0 && st2[row2[i]] != 0) { /* final: the stream stops at this frame */
+                stop = st2[row2[i]];
+                nc = i;
+                w.pos = chain[i].offset;
+                break;
+            }
+        }
+    }
+
+    /* 6. PCM: the frames that fit the caller's buffer */
+    std::vector<flacmi_pcm_frame> pf((size_t)nc);
+    int64_t first = 0;
+    for (int64_t i = 0; i < nc; ++i) {
+        if ((first + bsz[i]) * ch * B > pcm_capacity) { /* ends the call like a cut-off frame */
+            if (i == 0) return fail(FLACMI_E_NOMEM, "pcm_capacity %lld holds no frame of %d samples", (long long)pcm_capacity, bsz[i]);
+            nc = i;
+            stop = 0;
+            res->pcm_full = 1;
+            w.pos = chain[i].offset;
+            break;
+        }
+        const flacmi_chain_frame& c = chain[i];
+        flacmi_pcm_frame& f = pf[i];
+        if (row2[i] >= 0) {
+            f.rows = (int32_t*)rows2.p + row2[i] * ch * stride2;
+            f.stride = stride2;
+        } else {
+            f.rows = (int32_t*)ctx->sd_rows.p + c.candidate * ch * stride1;
+            f.stride = stride1;
+        }
+        f.first_sample = first;
+        f.block_size = bsz[i];
+        f.reserved0 = 0;
+        first += bsz[i];
+    }
+    if (nc > 0) {
+        const int64_t total = first * ch * B;
+        if (int rc = ensure_buf(ctx->sd_pcm, (size_t)total + 16)) return rc;
+        ScopedDev d_pf;
+        if (int rc = d_pf.alloc(sizeof(flacmi_pcm_frame) * (size_t)nc + 4 * (size_t)nc)) return rc;
+        int32_t* d_ps = (int32_t*)((char*)d_pf.p + sizeof(flacmi_pcm_frame) * (size_t)nc);
+        std::vector<int32_t> ps((size_t)nc);
+        HIP_TRY(hipMemcpyAsync(d_pf.p, pf.data(), sizeof(flacmi_pcm_frame) * (size_t)nc, hipMemcpyHostToDevice, s));
+        if (int rc = flacmi_pcm_out_device(ctx, (const flacmi_pcm_frame*)d_pf.p, nc, ch, B, mode, (uint8_t*)ctx->sd_pcm.p, total, d_ps, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(ps.data(), d_ps, sizeof(int32_t) * (size_t)nc, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int64_t i = 0; i < nc; ++i) {
+            if (ps[i] != 0) {
+                stop = (ps[i] & 0xFFFF) == FLACMI_STATUS_OVERFLOW ? ((FLACMI_DSITE_PCM_RANGE << 16) | FLACMI_STATUS_OVERFLOW) : ps[i];
+                nc = i;
+                w.pos = chain[i].offset;
+                first = pf[i].first_sample;
+                break;
+            }
+        }
+        /* 7. copy out */
+        if (first > 0) HIP_TRY(hipMemcpy(pcm, ctx->sd_pcm.p, (size_t)(first * ch * B), hipMemcpyDeviceToHost));
+    }
+    res->frames = nc;
+    res->samples = first;
+    res->pcm_bytes = first * ch * B;
+    res->consumed = w.pos;
+    res->status = stop & 0xFFFF;
+    res->site = (stop >> 16) & 0xFFFF;
     return 0;
 }
 

@@ -135,6 +135,73 @@ struct DecodeArgs {
     unsigned long long* defer2_count; /* the frames k_decode_fx's LPC pass hands on: count, */
     int64_t* defer2_list;             /* and their indices ([n_frames]) */
     int32_t lpc_pass;                 /* k_decode_fx's LPC pass runs (knob FLACMI_DECODE_LPC=0: off) */
+    int64_t* frame_end;               /* optional [n_frames]: the byte after the frame's footer where the
+                                         frame raised no reference exception, else -1 */
+};
+
+/* Frame index (k_index.hip): candidate frame starts of a byte stream, in stream order.  A tile
+ * is the bytes one workgroup reads (16 per lane); tiles count from the 16-byte boundary at or
+ * below the stream's base address. */
+constexpr int kIndexTile = 4096;
+struct IndexArgs {
+    const uint8_t* base;     /* 4-byte aligned */
+    int64_t bytes, first;    /* stream size; candidates at offsets >= first only */
+    int32_t mis;             /* base address & 15 */
+    int64_t n_tiles;         /* ceil((mis + bytes) / kIndexTile) */
+    flacmi_frame_candidate* table;
+    int64_t capacity;
+    int64_t* count;          /* the true count, whatever the capacity */
+    int32_t* tile_count;     /* workspace [n_tiles rounded up to 4] */
+    int32_t* tile_base;      /* workspace [n_tiles]: exclusive prefix inside the tile's scan group */
+    int64_t* group_base;     /* workspace [index_scan_groups(n_tiles)] */
+};
+
+/* Every header check of decode_general (k_decode.hip, decoder.py:133-185) at byte p, whose
+ * first two bytes are known to hold the sync code, plus (check_crc8) the CRC-8; reads bytes
+ * [p, bytes) only.  The device lists candidates with it (k_index.hip); the host reads the
+ * block size of a chain frame that is no candidate with it (flacmi_decode_stream_host). */
+__host__ __device__ inline bool parse_header(const uint8_t* s, int64_t bytes, int64_t p, bool check_crc8,
+                                             flacmi_frame_candidate& c) {
+    if (p + 6 > bytes) return false; /* sync, two code bytes, one number byte, CRC-8 */
+    const uint32_t b2 = s[p + 2], b3 = s[p + 3];
+    const int bcode = b2 >> 4, rcode = b2 & 15, ch = b3 >> 4, scode = (b3 >> 1) & 7;
+    if (bcode == 0 || bcode == 15 || rcode == 15 || ch > 10 || scode == 3 || (b3 & 1)) return false;
+    const uint32_t b0 = s[p + 4];
+    const int extra = b0 >= 0xFE ? 6 : b0 >= 0xFC ? 5 : b0 >= 0xF8 ? 4 : b0 >= 0xF0 ? 3 : b0 >= 0xE0 ? 2 : b0 >= 0xC0 ? 1 : 0;
+    const int nb = bcode == 6 ? 1 : bcode == 7 ? 2 : 0, nr = rcode == 12 ? 1 : rcode >= 13 ? 2 : 0;
+    const int n = 5 + extra + nb + nr; /* bytes the CRC-8 covers */
+    if (p + n + 1 > bytes) return false;
+    uint64_t fno = extra == 0 ? b0 : (b0 & ((1u << (6 - extra)) - 1));
+    for (int k = 0; k < extra; ++k) fno = (fno << 6) | (s[p + 5 + k] & 0x3F);
+    int bs;
+    if (bcode == 1) bs = 192;
+    else if (bcode <= 5) bs = 144 << bcode;
+    else if (bcode == 6) bs = (int)s[p + 5 + extra] + 1;
+    else if (bcode == 7) bs = (((int)s[p + 5 + extra] << 8) | s[p + 6 + extra]) + 1;
+    else bs = 1 << bcode;
+    uint32_t crc = 0; /* x^8 + x^2 + x + 1, init 0 */
+    for (int k = 0; k < n; ++k) {
+        crc ^= s[p + k];
+        for (int b = 0; b < 8; ++b) crc = (crc & 0x80) ? ((crc << 1) ^ 0x07) & 0xFF : (crc << 1) & 0xFF;
+    }
+    if (check_crc8 && crc != s[p + n]) return false;
+    c.offset = p;
+    c.coded_number = (int64_t)fno;
+    c.block_size = bs;
+    c.header_bytes = n + 1;
+    c.channel_code = ch;
+    c.sample_size_code = scode;
+    return true;
+}
+
+/* PCM writer (k_index.hip, k_pcm) */
+struct PcmArgs {
+    const flacmi_pcm_frame* frames;
+    int64_t n_frames;
+    int32_t channels, bytes_per_sample, raw;
+    uint8_t* out;            /* 4-byte aligned */
+    int64_t capacity;
+    int32_t* status;         /* [n_frames] */
 };
 
 struct ResidLaunch {
@@ -177,6 +244,9 @@ hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s);
 int64_t frame_scan_blocks(int64_t n_frames);
 hipError_t launch_pack(const FrameArgs& a, hipStream_t s);
 hipError_t launch_decode(DecodeArgs a, hipStream_t s);
+hipError_t launch_index(const IndexArgs& a, hipStream_t s);
+int64_t index_scan_groups(int64_t n_tiles);
+hipError_t launch_pcm(const PcmArgs& a, hipStream_t s);
 
 hipError_t launch_selftest(int32_t which, const double* x, double* out, int32_t* status, int64_t n,
                            const double* log2thr, hipStream_t s);

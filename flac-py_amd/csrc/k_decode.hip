@@ -222,7 +222,10 @@ __device__ uint32_t crc16_range(const DecodeArgs& a, const uint16_t* t, int64_t 
     return c;
 }
 
-/* The general decoder: frame f, every check, the reference's exception precedence. */
+/* The general decoder: frame f, every check, the reference's exception precedence.  END: the
+ * frame's end goes to a.frame_end (the stream decoder's first pass; the verifier's kernel is
+ * built without the store). */
+template <bool END>
 __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*ring)[kDecThreads],
                              int16_t (*coef)[kDecThreads], const uint16_t* crct, const int lane) {
     const int64_t F = a.offsets[f], Fend = a.offsets[f + 1];
@@ -442,6 +445,7 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
         }
         if (is_ref_error(st)) break;
     }
+    int64_t fend = -1; /* a.frame_end: where the parse ended (known once the footer is read) */
     if (!is_ref_error(st) && nch > 0) {
         /* footer (decoder.py:124-128): zero padding to a byte, CRC-16 */
         if (g.pos() & 7) {
@@ -450,6 +454,7 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
         const uint32_t crc16 = g.uint(16);
         if (g.pos() > end_bit) fail(DS_EOF);
         else {
+            fend = g.pos() >> 3;
             if ((g.pos() >> 3) != Fend) fail(DS_FRAME_END);
             if (a.check_crc) {
                 uint32_t c;
@@ -469,10 +474,14 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
     if (bad) fail(DS_SAMPLES);
     a.status[f] = st;
     a.mismatch[f] = bad;
-    a.decorr[f] = (decorr && !is_ref_error(st)) ? ((bs << 8) | ch_code) : 0;
+    /* nch == 0: nothing was decoded (a block larger than the rows, a channel-count finding), so
+     * there is nothing to recombine, and bs may exceed the rows k_decorr would walk */
+    a.decorr[f] = (decorr && !is_ref_error(st) && nch > 0) ? ((bs << 8) | ch_code) : 0;
+    if (END) a.frame_end[f] = is_ref_error(st) ? -1 : fend;
 }
 
 /* The frames k_decode_fx listed (a.defer_all: every frame), one lane each. */
+template <bool END>
 __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
     __shared__ int32_t ring[kRingSlots][kDecThreads];
     __shared__ int16_t coef[kRingSlots][kDecThreads]; /* precision <= 15 bits (4-bit field, 15 rejected) */
@@ -482,7 +491,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
     __syncthreads();
     const int64_t nl = a.defer_all ? a.n_frames : (int64_t)*a.defer_count;
     for (int64_t k = (int64_t)blockIdx.x * kDecThreads + lane; k < nl; k += (int64_t)gridDim.x * kDecThreads)
-        decode_general(a, a.defer_all ? k : a.defer_list[k], ring, coef, crct, lane);
+        decode_general<END>(a, a.defer_all ? k : a.defer_list[k], ring, coef, crct, lane);
 }
 
 constexpr int kFxThreads = 256; /* k_decode_fx: frames per workgroup (one CRC table copy) */
@@ -1082,6 +1091,10 @@ __global__ __launch_bounds__(256) void k_decorr(DecodeArgs a) {
 
 hipError_t launch_decode(DecodeArgs a, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
+    if (a.frame_end) { /* a frame k_decode_fx accepts ends at offsets[f + 1]; k_decode writes the others' */
+        hipError_t e = hipMemcpyAsync(a.frame_end, a.offsets + 1, sizeof(int64_t) * (size_t)a.n_frames, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return e;
+    }
     int64_t blocks = (a.n_frames + kDecThreads - 1) / kDecThreads;
     if (!a.defer_all && !(a.expect && !a.expect_vec) && !(a.out && (a.out_stride & 3))) {
         hipError_t e = hipMemsetAsync(a.defer_count, 0, sizeof(unsigned long long), s);
@@ -1117,7 +1130,8 @@ hipError_t launch_decode(DecodeArgs a, hipStream_t s) {
     } else {
         a.defer_all = 1; /* rows k_decode_fx cannot read with 16-byte accesses: every frame general */
     }
-    hipLaunchKernelGGL(k_decode, dim3((unsigned)blocks), dim3(kDecThreads), 0, s, a);
+    if (a.frame_end) hipLaunchKernelGGL(k_decode<true>, dim3((unsigned)blocks), dim3(kDecThreads), 0, s, a);
+    else hipLaunchKernelGGL(k_decode<false>, dim3((unsigned)blocks), dim3(kDecThreads), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !a.out) return e;
     hipLaunchKernelGGL(k_decorr, dim3((unsigned)a.n_frames), dim3(256), 0, s, a);

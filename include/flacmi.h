@@ -355,6 +355,7 @@ enum flacmi_decode_site {
     FLACMI_DSITE_BLOCK_SIZE,         /* verifier: block size != the expected unit length / out_stride */
     FLACMI_DSITE_CHANNELS,           /* verifier: header channel count != dp->channels */
     FLACMI_DSITE_SAMPLES,            /* verifier: decoded samples differ from `expect` */
+    FLACMI_DSITE_PCM_RANGE,          /* __main__.py:46  to_bytes: a sample does not fit the PCM width (OverflowError) */
 };
 typedef struct flacmi_decode_params {
     int32_t channels;        /* subframes per frame (STREAMINFO channels), 1..8 */
@@ -375,6 +376,151 @@ int flacmi_decode_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int
                                 const flacmi_decode_params* dp, const flacmi_batch* expect,
                                 int32_t* samples_out, int64_t out_stride, int32_t* frame_status,
                                 int64_t* frame_mismatch, void* stream);
+
+/* The same, and frame_end[n_frames] (device pointer, or NULL: exactly the call above)
+ * receives per frame the byte offset after its CRC-16 footer, i.e. where the reference's
+ * reader stands after get_frame (decoder.py:111-130), or -1 where the frame raised a
+ * reference exception or was not parsed to its end (a FLACMI_DSITE_BLOCK_SIZE /
+ * FLACMI_DSITE_CHANNELS finding).  The parse does not depend on frame_offsets[f + 1]; only
+ * the FLACMI_DSITE_FRAME_END finding does, so a caller who does not know where frames end
+ * proposes any end and reads the true one here. */
+int flacmi_decode_frames_end_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                                    const int64_t* frame_offsets, int64_t n_frames,
+                                    const flacmi_decode_params* dp, const flacmi_batch* expect,
+                                    int32_t* samples_out, int64_t out_stride, int32_t* frame_status,
+                                    int64_t* frame_mismatch, int64_t* frame_end, void* stream);
+
+/* ---- stream decoder: .flac bytes in, interleaved PCM out ---------------------------- */
+/* Replaces the reference's decode loop: decoder.py:46-55 samples() over get_frames
+ * (:100-108), and cmd_decode's to_bytes loop (__main__.py:45-50).  The reference learns
+ * where a frame starts by decoding every frame before it.  Here the device lists every
+ * position that could start a frame (a "candidate"), decodes all of them at once, and the
+ * host walks the chain of true frames through the decoded ends ("Stream
+ * decoder").
+ *
+ * A byte offset p >= first_byte is a candidate iff the bytes at p pass every header check of
+ * get_frame_header (decoder.py:133-185: 15-bit sync, block-size code 1..14, sample-rate code
+ * != 15, channel code <= 10, sample-size code != 3, reserved bit 0; the coded number read as
+ * following_bytes says, continuation prefixes unchecked), the header with its CRC-8 byte lies
+ * inside stream_bytes, and the CRC-8 (crc.py:18-22) of the header matches. */
+typedef struct flacmi_frame_candidate {
+    int64_t offset;           /* byte offset of the sync code */
+    int64_t coded_number;     /* frame or sample number (coded_number.py:45-70) */
+    int32_t block_size;       /* samples per channel */
+    int32_t header_bytes;     /* header length, CRC-8 byte included */
+    int32_t channel_code;     /* 0..10 */
+    int32_t sample_size_code; /* 0..7 except 3 */
+} flacmi_frame_candidate;
+/* Bytes of the stream one workgroup of the index kernel scans; tiles count from the 16-byte
+ * boundary at or below stream_data.  For tests that place headers across tile edges. */
+int32_t flacmi_index_tile_bytes(void);
+/* Device pointers, enqueued on `stream`.  table[capacity] receives the candidates in strictly
+ * ascending offset order; *count always receives the true count: when it exceeds capacity
+ * the table holds the first `capacity` candidates and the caller retries with a larger
+ * table (at most stream_bytes / 2 candidates exist). */
+int flacmi_index_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                               int64_t first_byte, flacmi_frame_candidate* table, int64_t capacity,
+                               int64_t* count, void* stream);
+
+/* One frame of decoded rows for flacmi_pcm_out_device: channel c's samples are
+ * rows[c * stride .. c * stride + block_size) (device int32). */
+typedef struct flacmi_pcm_frame {
+    const void* rows;
+    int64_t stride;
+    int64_t first_sample;    /* samples per channel in the frames before it */
+    int32_t block_size;
+    int32_t reserved0;
+} flacmi_pcm_frame;
+enum flacmi_pcm_mode {
+    FLACMI_PCM_PACKED = 0,   /* bytes_per_sample little-endian two's complement bytes per sample */
+    FLACMI_PCM_RAW32 = 1,    /* int32 per sample, no range check (bytes_per_sample ignored) */
+};
+/* Interleave (decoder.py:52 zip(*samples)) and pack (__main__.py:46-50 to_bytes): sample t of
+ * channel c of a frame goes to out[((first_sample + t) * channels + c) * B ..), B =
+ * bytes_per_sample (1..4) or 4 in raw mode.  frame_status[f] = FLACMI_STATUS_OVERFLOW where a
+ * sample does not fit 8 B signed bits (to_bytes raises OverflowError; the frame's bytes are
+ * then unspecified), FLACMI_STATUS_FRAME_TOO_LARGE where the frame does not lie inside
+ * out_capacity (nothing written), else 0.  Device pointers (out 4-byte aligned), enqueued
+ * on `stream`. */
+int flacmi_pcm_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64_t n_frames,
+                          int32_t channels, int32_t bytes_per_sample, int32_t mode, uint8_t* out,
+                          int64_t out_capacity, int32_t* frame_status, void* stream);
+
+/* The walk from frame to frame over the candidate table and the first pass's results (plain
+ * host code, no device: get_frames' loop, decoder.py:100-108, with each frame's end looked
+ * up instead of reached by reading).  status[k] / frame_end[k] are candidate k's results from
+ * flacmi_decode_frames_end_device with frame k proposed to end at candidate k + 1 (or
+ * stream_bytes).  Start with w->pos = first_byte, n_chain = 0, state = FLACMI_WALK_RUN.
+ * Each call appends chain frames until
+ *   FLACMI_WALK_DONE    the stream's end, or an EOFError frame (silent, as get_frames): w->pos
+ *                       is the offset after the last whole frame;
+ *   FLACMI_WALK_STOPPED any other reference exception, or a frame that cannot be parsed to its
+ *                       end: w->stop_status = (site << 16) | status, the frame at w->pos;
+ *   FLACMI_WALK_PROBE   w->pos is no candidate (a true header whose CRC-8 byte is wrong, which
+ *                       the reference reads unchecked, or whatever follows a frame), or its block
+ *                       exceeds the first pass's rows: the caller decodes the one frame
+ *                       [w->pos, stream_bytes), stores its status and end in w->probe_status /
+ *                       w->probe_end and calls again (every probe moves w->pos on: a stream whose
+ *                       headers mostly fail CRC-8 decodes correctly, one launch per frame);
+ *   FLACMI_WALK_FULL    chain_capacity reached: call again with more room.
+ * Candidates the walk never lands on are false syncs inside frame data. */
+enum flacmi_walk_state { FLACMI_WALK_RUN = 0, FLACMI_WALK_DONE = 1, FLACMI_WALK_STOPPED = 2,
+                         FLACMI_WALK_PROBE = 3, FLACMI_WALK_FULL = 4 };
+typedef struct flacmi_chain_frame {
+    int64_t offset, end;     /* the frame is bytes [offset, end) */
+    int64_t candidate;       /* its index in the table, or -1: an inserted start */
+    int32_t status;          /* first-pass (or probe) status word; 0: decoded rows are final */
+    int32_t reserved0;
+} flacmi_chain_frame;
+typedef struct flacmi_walk {
+    int64_t pos;
+    int64_t n_chain;
+    int32_t state;           /* flacmi_walk_state */
+    int32_t stop_status;
+    int32_t probe_status;
+    int32_t reserved0;
+    int64_t probe_end;
+} flacmi_walk;
+int flacmi_host_chain_walk(const flacmi_frame_candidate* table, int64_t n_candidates, const int32_t* status,
+                           const int64_t* frame_end, int64_t stream_bytes, int32_t final_chunk,
+                           flacmi_walk* w, flacmi_chain_frame* chain, int64_t chain_capacity);
+
+/* One chunk of a stream, host bytes in, host PCM out (synchronous): copy in, index, decode
+ * every candidate (pass 1, frame k proposed to end at candidate k + 1, rows k * channels ..
+ * at the pitch of max_block_size, STREAMINFO's, or of the largest block a candidate declares
+ * when that is 0), the walk, pass 2 (every chain frame whose pass-1 status was not 0, i.e. a
+ * false candidate inside it, an inserted start or an oversized block, again with the
+ * chain's own offsets into rows of their own pitch; its status is final), the PCM kernel,
+ * copy out.  dp->first_frame is not checked (the reference never checks frame numbers);
+ * with dp->check_crc = 0, the reference's behaviour, no CRC finding can occur; with 1 a
+ * finding stops the stream at that frame like an exception.  The verifier's two documented
+ * choices hold (above FLACMI_STATUS_EOF).
+ *
+ * data[0 .. bytes) is the chunk, frames start at first_byte; final_chunk = 0 says more bytes
+ * follow, so a frame the chunk cuts off ends the call with res->consumed at its start (the
+ * caller carries the tail over), where the final chunk ends silently as get_frames does.
+ * pcm[pcm_capacity] receives the frames that fit whole; the first that does not ends the
+ * call like a cut-off frame.  A frame whose samples overflow the PCM width stops the stream
+ * with FLACMI_STATUS_OVERFLOW / FLACMI_DSITE_PCM_RANGE; the frames before it are delivered,
+ * none of its own samples (the reference writes the frame's samples up to the failing one
+ * before raising: the difference is frame-granular).  FLACMI_E_UNSUPPORTED when the
+ * candidates' rows would exceed 4 GiB: pass a smaller chunk. */
+typedef struct flacmi_stream_result {
+    int64_t frames;          /* frames delivered */
+    int64_t samples;         /* samples per channel delivered */
+    int64_t pcm_bytes;       /* bytes written to pcm */
+    int64_t consumed;        /* offset after the last delivered frame */
+    int32_t status, site;    /* why the stream stopped: 0, 0 = it has not (end of chunk or stream) */
+    int64_t candidates;      /* k_index's count */
+    int64_t probes;          /* inserted starts and oversized blocks decoded one by one */
+    int64_t pass2_frames;    /* chain frames decoded again */
+    int64_t pcm_full;        /* 1: the call ended because the next frame does not fit pcm_capacity */
+    int64_t reserved0;
+} flacmi_stream_result;
+int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                              const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
+                              uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
+                              flacmi_stream_result* res);
 
 /* ---- stream statistics (reduced across GPUs with one RCCL all-reduce) ------------- */
 #define FLACMI_STATS_WORDS 128
