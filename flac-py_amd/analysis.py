@@ -32,8 +32,14 @@ def make_params(max_lpc_order: int, qlp_precision: int, rice_min: int, rice_max:
     return p
 
 
-def frame_params(channels: int, sample_size: int, qlp_precision: int, first_frame: int = 0) -> abi.FrameParams:
+def frame_params(channels: int, sample_size: int, qlp_precision: int, first_frame: int = 0,
+                 fallback: bool = False, sub_kind_ptr: int = 0) -> abi.FrameParams:
+    """fallback: FLACMI_FRAME_FALLBACK (a unit the reference cannot write, or writes larger than
+    raw, becomes a CONSTANT / VERBATIM subframe); sub_kind_ptr: the device int32 [n_units] array
+    the *_device entry points then need (the host entry points keep their own)."""
     fp = abi.FrameParams()
+    fp.reserved0 = abi.FRAME_FALLBACK if fallback else 0
+    fp.reserved[0] = sub_kind_ptr
     fp.channels = channels
     fp.sample_size = sample_size
     fp.qlp_precision = qlp_precision
@@ -209,8 +215,9 @@ class Analyzer:
     # ------------------------------------------------------------------------------
     def encode_frames(self, samples: np.ndarray, params: abi.Params, block_len: int, tail_len: int = 0,
                       n_tail_units: int = 0, sample_bits: int = 16, channels: int = 1,
-                      sample_size: int = 16, first_frame: int = 0):
+                      sample_size: int = 16, first_frame: int = 0, fallback: bool = False):
         """Host rows in -> (frame bytes, frame offsets [n_frames + 1], frame status [n_frames]).
+        fallback: see frame_params.
 
         Row f*channels + c is channel c of frame f.  A frame whose status is non-zero
         (the reference's exception, (site << 16) | status) has no bytes."""
@@ -227,7 +234,7 @@ class Analyzer:
         b.block_len = block_len
         b.tail_len = tail_len
         b.n_tail_units = n_tail_units
-        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame)
+        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback)
         n_frames = n_units // channels if channels else 0
         offsets = np.zeros(n_frames + 1, dtype=np.int64)
         status = np.zeros(max(n_frames, 1), dtype=np.int32)
@@ -241,7 +248,7 @@ class Analyzer:
     def encode_pipeline(self, samples: np.ndarray, params: abi.Params, block_len: int, tail_len: int = 0,
                         n_tail_units: int = 0, sample_bits: int = 16, channels: int = 1, sample_size: int = 16,
                         first_frame: int = 0, units_per_batch: int = 8192, capacity: int = 0,
-                        out: np.ndarray = None):
+                        out: np.ndarray = None, fallback: bool = False):
         """encode_frames through flacmi_encode_pipeline: host rows in (any row stride), the
         batch streamed through the device in sub-batches of units_per_batch units with the
         PCIe copies overlapping the kernels.  `out` (optional, uint8): the caller's frame
@@ -264,7 +271,7 @@ class Analyzer:
         b.block_len = block_len
         b.tail_len = tail_len
         b.n_tail_units = n_tail_units
-        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame)
+        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback)
         n_frames = n_units // channels if channels else 0
         offsets = np.zeros(n_frames + 1, dtype=np.int64)
         status = np.zeros(max(n_frames, 1), dtype=np.int32)

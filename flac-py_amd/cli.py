@@ -5,7 +5,7 @@ frame writer through the streaming pipeline (encoder.encode_wav); --devices spre
 batches over several GPUs.
 
     python -m flac_amd encode infile.wav outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
-                                                       [--correct-reader] [--fixed-only]
+                                                       [--correct-reader] [--fixed-only] [--fallback]
                                                        [--device N | --devices N,M,...]
 
     python -m flac_amd decode infile.flac outfile.wav [--device N] [--check-crc]
@@ -42,6 +42,9 @@ def make_argument_parser():
     enc.add_argument("--correct-reader", action="store_true",
                      help="read sampwidth-byte samples (the reference groups frame bytes by channel count)")
     enc.add_argument("--fixed-only", action="store_true", help="fixed predictors only (BASELINE config 5)")
+    enc.add_argument("--fallback", action="store_true",
+                     help="write a subframe the reference cannot write (digital silence, ...) or writes larger "
+                          "than raw as CONSTANT / VERBATIM instead of stopping at its frame")
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
@@ -68,7 +71,7 @@ def cmd_encode(args) -> None:
     t0 = timer()
     with args.outfile.open("wb") as f:
         for bs in encode_wav(args.infile, parameters, quirk=not args.correct_reader, device=args.device,
-                             devices=args.devices, fixed_only=args.fixed_only):
+                             devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback):
             f.write(bs)
     print(f"Encoding completed in {timer() - t0:.6g} seconds")
 

@@ -164,6 +164,7 @@ struct flacmi_ctx {
     DevBuf rec, retry, h_samples, h_meta, h_params, h_residual, h_acf, h_fs, h_ls, h_recs;
     uint16_t* d_crc = nullptr;  /* CRC-16 slice tables [4][256] + power tables [28][512] */
     DevBuf scan, h_offsets, h_status, h_frames, dec, slow;
+    DevBuf h_subkind;           /* flacmi_encode_host's sub_kind array (FLACMI_FRAME_FALLBACK) */
     DevBuf idx, sd_data, sd_table, sd_meta, sd_rows, sd_pcm; /* frame index workspace; flacmi_decode_stream_host's buffers */
     int64_t frames_bytes = 0;   /* bytes of the last flacmi_encode_host call */
     static constexpr int kRing = 64;
@@ -312,7 +313,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     for (auto& kv : ctx->windows) (void)hipFree(kv.second);
     for (DevBuf* b : {&ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
-                      &ctx->h_frames})
+                      &ctx->h_frames, &ctx->h_subkind})
         if (b->p) (void)hipFree(b->p);
     if (ctx->d_log2thr) (void)hipFree(ctx->d_log2thr);
     if (ctx->d_sintab) (void)hipFree(ctx->d_sintab);
@@ -761,6 +762,8 @@ static int validate_frames(const flacmi_batch* b, const flacmi_frame_params* fp,
     if (fp->sample_size < 1 || fp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 1..32");
     if (fp->qlp_precision < 5 || fp->qlp_precision > 31) return fail(FLACMI_E_INVALID, "qlp_precision must be 5..31");
     if (fp->first_frame < 0) return fail(FLACMI_E_INVALID, "first_frame must be >= 0");
+    if (fp->reserved0 & ~FLACMI_FRAME_FALLBACK)
+        return fail(FLACMI_E_INVALID, "unknown frame flag bits %#x (reserved0)", (unsigned)fp->reserved0);
     if (b->n_units % fp->channels != 0) return fail(FLACMI_E_INVALID, "n_units must be a multiple of channels");
     if (b->n_tail_units != 0 && b->n_tail_units != fp->channels)
         return fail(FLACMI_E_INVALID, "the short last frame must hold exactly `channels` tail units");
@@ -791,6 +794,23 @@ static FrameArgs frame_args(flacmi_ctx* ctx, const flacmi_batch* b, const flacmi
     a.crc_slice = ctx->d_crc;
     a.crc_pow = ctx->d_crc + 4 * 256;
     return a;
+}
+
+/* FLACMI_FRAME_FALLBACK at the *_device entry points: the caller's sub_kind array */
+static int caller_sub_kind(const flacmi_frame_params* fp, FrameArgs& a) {
+    if (!(fp->reserved0 & FLACMI_FRAME_FALLBACK)) return 0;
+    a.sub_kind = (int32_t*)(uintptr_t)fp->reserved[0];
+    if (!a.sub_kind) return fail(FLACMI_E_INVALID, "FLACMI_FRAME_FALLBACK needs a sub_kind array in reserved[0]");
+    return 0;
+}
+
+/* the same for the host entry points: an array of their own (a context buffer, or one per
+ * pipeline slot) */
+static int own_sub_kind(const flacmi_frame_params* fp, DevBuf& buf, FrameArgs& a) {
+    if (!(fp->reserved0 & FLACMI_FRAME_FALLBACK)) return 0;
+    if (int rc = ensure_buf(buf, sizeof(int32_t) * (size_t)a.n_units)) return rc;
+    a.sub_kind = (int32_t*)buf.p;
+    return 0;
 }
 
 /* the k_pack32 -> k_pack hand-off list (count word + one index per frame) */
@@ -824,6 +844,7 @@ int flacmi_frame_sizes_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
         return 0;
     }
     FrameArgs a = frame_args(ctx, batch, fp, meta, rice_params, params_stride, nf);
+    if (int rc = caller_sub_kind(fp, a)) return rc;
     return frame_sizes_impl(ctx, a, frame_offsets, frame_status, (hipStream_t)stream);
 }
 
@@ -843,6 +864,7 @@ int flacmi_pack_frames_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
     if (nf == 0) return 0;
     if (int rc = set_device(ctx)) return rc;
     FrameArgs a = frame_args(ctx, batch, fp, meta, rice_params, params_stride, nf);
+    if (int rc = caller_sub_kind(fp, a)) return rc;
     a.residual = residual;
     a.residual_bytes = residual_bytes;
     a.residual_stride = residual_stride;
@@ -1374,6 +1396,7 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
         if (int rc = validate(&db, params, &o)) return rc;
         if (int rc = analyze_device_impl(ctx, &db, params, &o, ctx->stream)) return rc;
         FrameArgs a = frame_args(ctx, &db, fp, o.meta, o.rice_params, pstride, nf);
+        if (int rc = own_sub_kind(fp, ctx->h_subkind, a)) return rc;
         if (int rc = frame_sizes_impl(ctx, a, (int64_t*)ctx->h_offsets.p, (int32_t*)ctx->h_status.p, ctx->stream))
             return rc;
         HIP_TRY(hipMemcpyAsync(frame_offsets, ctx->h_offsets.p, sizeof(int64_t) * (nf + 1), hipMemcpyDeviceToHost,
@@ -1421,6 +1444,7 @@ namespace {
 constexpr int kEncSlots = 4; /* with 3 the host waited for the D2H of sub-batch k - 3 before issuing the H2D of k */
 struct EncSlot {
     DevBuf samples, meta, params, residual, offsets, status, frames;
+    DevBuf subkind;             /* sub_kind of the sub-batch's units (FLACMI_FRAME_FALLBACK) */
     int64_t* h_off = nullptr;   /* pinned, mapped: frame offsets of the sub-batch */
     int32_t* h_st = nullptr;    /* pinned, mapped: frame status */
     int64_t* d_off = nullptr;   /* their device-side addresses (k_export writes them) */
@@ -1449,7 +1473,8 @@ static void enc_free(EncState* es) {
     for (hipStream_t st : {es->is, es->os})
         if (st) (void)hipStreamSynchronize(st);
     for (auto& sl : es->slot) {
-        for (DevBuf* d : {&sl.samples, &sl.meta, &sl.params, &sl.residual, &sl.offsets, &sl.status, &sl.frames})
+        for (DevBuf* d : {&sl.samples, &sl.meta, &sl.params, &sl.residual, &sl.offsets, &sl.status, &sl.frames,
+                          &sl.subkind})
             if (d->p) (void)hipFree(d->p);
         if (sl.h_off) (void)hipHostFree(sl.h_off);
         if (sl.h_st) (void)hipHostFree(sl.h_st);
@@ -1551,6 +1576,7 @@ static int enc_front(flacmi_ctx* ctx, EncSlot& sl, const flacmi_batch* whole, co
     flacmi_frame_params f = *fp;
     f.first_frame = fp->first_frame + sl.first_unit / fp->channels;
     FrameArgs a = frame_args(ctx, &db, &f, o.meta, o.rice_params, pstride, sl.nf);
+    if (int rc = own_sub_kind(fp, sl.subkind, a)) return rc;
     if (int rc = frame_sizes_impl(ctx, a, (int64_t*)sl.offsets.p, (int32_t*)sl.status.p, cs)) return rc;
     HIP_TRY(hipEventRecord(sl.e[3], cs));
     HIP_TRY(launch_export((const int64_t*)sl.offsets.p, (const int32_t*)sl.status.p, sl.nf, sl.d_off, sl.d_st, cs));
@@ -1684,6 +1710,7 @@ extern "C" int flacmi_encode_pipeline(flacmi_ctx* ctx, const flacmi_batch* batch
             f.first_frame = fp->first_frame + f0;
             FrameArgs a = frame_args(ctx, &db, &f, (const flacmi_unit_meta*)sl.meta.p, (const int32_t*)sl.params.p,
                                      pstride, sl.nf);
+            if (int r = own_sub_kind(fp, sl.subkind, a)) return r; /* the array enc_front's k_sub_kinds wrote */
             a.residual = sl.residual.p;
             a.residual_bytes = sl.rbytes;
             a.residual_stride = rstride;

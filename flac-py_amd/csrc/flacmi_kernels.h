@@ -106,6 +106,8 @@ struct FrameArgs {
     int64_t* slow_list;              /* and their indices ([n_frames]) */
     int32_t ablate;            /* profiling only (env FLACMI_PACK_ABLATE): 1 no CRC shift, 2 no residual codes,
                                   3 neither (output invalid) */
+    int32_t* sub_kind;         /* FLACMI_FRAME_FALLBACK: [n_units] flacmi_sub_kind, written by k_sub_kinds and
+                                  read by k_frame_sizes and the writers; NULL: the mode is off */
 };
 
 /* Decoder verifier (k_decode.hip): frame f = bytes [offsets[f], offsets[f+1]) of words. */
@@ -239,7 +241,8 @@ hipError_t launch_synth(void* dst, int32_t sample_bytes, int32_t bits, int64_t s
 hipError_t launch_stats(const flacmi_unit_meta* meta, int64_t n_units, int32_t block_len,
                         int32_t tail_len, int64_t n_tail_units, int64_t* stats, hipStream_t s);
 
-/* frame sizes + exclusive scan into a.offsets; bsum: frame_scan_blocks(n_frames) words */
+/* (a.sub_kind set: k_sub_kinds first,) frame sizes + exclusive scan into a.offsets; bsum:
+ * frame_scan_blocks(n_frames) words */
 hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s);
 int64_t frame_scan_blocks(int64_t n_frames);
 hipError_t launch_pack(const FrameArgs& a, hipStream_t s);

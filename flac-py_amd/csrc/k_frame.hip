@@ -16,6 +16,12 @@
  *                  header bits per partition; the written size differs from it by a
  *                  closed form), the frame's status (first reference exception), then a
  *                  three-kernel exclusive scan gives every frame its byte offset.
+ *   k_sub_kinds    (fallback mode only, FLACMI_FRAME_FALLBACK) one wave per unit, before
+ *                  k_frame_sizes: which units the reference cannot write, or writes larger
+ *                  than raw, and so become CONSTANT / VERBATIM subframes (encoder.py:559-578,
+ *                  the writers the reference never calls).  k_frame_sizes and k_pack take the
+ *                  sizes and the subframes from its sub_kind array; the two fast writers
+ *                  below hand such frames to k_pack by list.
  *   k_pack         one workgroup per frame.  Every field is OR-ed into an LDS window of
  *                  kWinWords 32-bit words at its exact bit position (positions from a
  *                  workgroup scan of per-value code lengths, 8 values per thread); a full
@@ -120,10 +126,89 @@ __device__ __forceinline__ int64_t sub_residual_bits(const flacmi_unit_meta& m, 
     return m.coding_method == 5 ? m.rice_bits - 3LL * m.n_parts - cnt14 : m.rice_bits - 4LL * m.n_parts;
 }
 
+/* What unit u is written as.  FB: the build of a kernel for the fallback mode (a.sub_kind
+ * set); the builds for the mode off never look at the array, so they are the code they were
+ * before the mode existed (an a.sub_kind test at run time cost k_packw2k 0.6% and
+ * k_frame_sizes 5% on config 2's frames). */
+template <bool FB>
+__device__ __forceinline__ int sub_kind_of(const FrameArgs& a, int64_t u) {
+    if constexpr (FB) return a.sub_kind[u];
+    else return 0;
+}
+
+/* Bits of a CONSTANT / VERBATIM subframe (encoder.py:553-578): the header byte and one or n
+ * samples of ss bits. */
+__device__ __forceinline__ uint32_t sub_raw_bits(int kind, int n, int ss) {
+    return 8u + (kind == FLACMI_SUB_CONSTANT ? 1u : (uint32_t)n) * (uint32_t)ss;
+}
+
+/* ====================================================================================
+ * k_sub_kinds: one wave per unit (fallback mode only)
+ *
+ * sub_kind[u] = 0 for a unit that stays as analysed, which is decided from the unit's meta
+ * alone (and, for Rice5Bit, its parameters, as k_frame_sizes counts them).  An escaped unit is
+ * CONSTANT when its n samples are all equal, else VERBATIM.  A constant block always fails in
+ * the reference (its best fixed residual is all zeros, so find_rice_parameter takes log2(0),
+ * or the LPC path has raised before), so only units with a nonzero status are scanned; a unit
+ * escaped for its size or for the precision assertion is VERBATIM without reading its row.
+ * ==================================================================================== */
+__global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= a.n_units) return;
+    const flacmi_unit_meta& m = a.meta[u];
+    const int n = unit_len(a, u);
+    const int st = m.status;
+    bool esc;
+    if (st != 0) {
+        esc = st == FLACMI_STATUS_ZERO_DIVISION || st == FLACMI_STATUS_ASSERTION || st == FLACMI_STATUS_VALUE_ERROR ||
+              st == FLACMI_STATUS_OVERFLOW;
+    } else if (m.kind == FLACMI_KIND_LPC && ((a.q - 1) & 15) == 15) {
+        esc = true;
+    } else {
+        int cnt = 0;
+        if (m.coding_method == 5) {
+            const int32_t* rp = a.rice_params + u * a.params_stride;
+            for (int k = lane; k < m.n_parts; k += 64) cnt += rp[k] > 14 ? 1 : 0;
+            for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+        }
+        esc = (int64_t)sub_prefix_bits(m, a.sample_size, a.q) + sub_residual_bits(m, cnt) >
+              8 + (int64_t)n * a.sample_size;
+    }
+    if (!esc || st == 0) {
+        if (lane == 0) a.sub_kind[u] = esc ? FLACMI_SUB_VERBATIM : FLACMI_SUB_ANALYSED;
+        return;
+    }
+    /* all samples equal to the first?  16-byte loads over the row's aligned middle, single
+     * samples before and behind it; the wave stops at the first 1024-byte step with a mismatch */
+    const int sb = a.sample_bytes;
+    const uint8_t* row = (const uint8_t*)a.samples + u * a.stride * sb;
+    const int per = 16 / sb; /* samples a 16-byte load */
+    int head = (int)((16 - ((uintptr_t)row & 15)) & 15) / sb;
+    head = head < n ? head : n;
+    const int nvec = (n - head) / per;
+    const int32_t x0 = sb == 2 ? (int32_t)((const int16_t*)row)[0] : ((const int32_t*)row)[0];
+    const uint32_t pat = sb == 2 ? ((uint32_t)(uint16_t)x0 * 0x10001u) : (uint32_t)x0;
+    auto sample = [&](int i) { return sb == 2 ? (int32_t)((const int16_t*)row)[i] : ((const int32_t*)row)[i]; };
+    bool diff = false;
+    for (int i = lane; i < head; i += 64) diff |= sample(i) != x0;
+    for (int i = head + nvec * per + lane; i < n; i += 64) diff |= sample(i) != x0;
+    const uint4* vrow = (const uint4*)(row + (size_t)head * sb);
+    for (int v0 = 0; v0 < nvec && !__any(diff); v0 += 64) {
+        if (v0 + lane < nvec) {
+            const uint4 w = vrow[v0 + lane];
+            diff |= ((w.x ^ pat) | (w.y ^ pat) | (w.z ^ pat) | (w.w ^ pat)) != 0;
+        }
+    }
+    const bool any_diff = __any(diff);
+    if (lane == 0) a.sub_kind[u] = any_diff ? FLACMI_SUB_VERBATIM : FLACMI_SUB_CONSTANT;
+}
+
 /* ====================================================================================
  * k_frame_sizes: one wave per frame
  * ==================================================================================== */
-__global__ __launch_bounds__(256) void k_frame_sizes(FrameArgs a) {
+template <bool FB>
+__device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
     const int lane = threadIdx.x & 63;
     const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (f >= a.n_frames) return;
@@ -136,6 +221,10 @@ __global__ __launch_bounds__(256) void k_frame_sizes(FrameArgs a) {
     int64_t bits = 0;
     for (int c = 0; c < a.channels && st == 0; ++c) {
         const flacmi_unit_meta& m = a.meta[u0 + c];
+        if (const int kind = sub_kind_of<FB>(a, u0 + c)) { /* escaped: no status, no meta */
+            bits += sub_raw_bits(kind, bs, a.sample_size);
+            continue;
+        }
         if (m.status != 0) {
             st = (m.site << 16) | m.status;
             break;
@@ -166,6 +255,8 @@ __global__ __launch_bounds__(256) void k_frame_sizes(FrameArgs a) {
         if (f == 0) a.offsets[0] = 0;
     }
 }
+__global__ __launch_bounds__(256) void k_frame_sizes(FrameArgs a) { frame_sizes<false>(a); }
+__global__ __launch_bounds__(256) void k_frame_sizes_fb(FrameArgs a) { frame_sizes<true>(a); }
 
 /* ---- exclusive scan of frame sizes (in place on offsets[1..n]) ---------------------- */
 constexpr int kScanItems = 8;
@@ -329,17 +420,19 @@ __device__ void win_flush(const FrameArgs& a, uint32_t* win, const uint16_t* ct,
  * partition boundary); the launch guarantees 32-bit residuals and <= kMaxC chunks per
  * thread. */
 constexpr int kMaxC = 4;
+template <bool FB>
 __device__ __forceinline__ bool pack32_frame_ok(const FrameArgs& a, int64_t f, int ww) {
     const int64_t bytes = a.offsets[f + 1] - a.offsets[f];
     if (bytes + 8 > 4LL * ww) return false;
     for (int c = 0; c < a.channels; ++c) {
         const int64_t u = f * a.channels + c;
+        if (sub_kind_of<FB>(a, u) != 0) return false; /* CONSTANT / VERBATIM: k_pack alone writes them */
         if ((unit_len(a, u) >> a.meta[u].part_order) < 8) return false;
     }
     return true;
 }
 
-template <typename ZT>
+template <typename ZT, bool FB>
 __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) {
     __shared__ uint32_t win[kWinWords];
     __shared__ uint16_t ct[4 * 256];
@@ -360,7 +453,7 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
     __syncthreads();
     for (int c = 0; c < C; ++c) {
         const flacmi_unit_meta& m = a.meta[u0 + c];
-        if (m.coding_method == 5) {
+        if (sub_kind_of<FB>(a, u0 + c) == 0 && m.coding_method == 5) { /* an escaped unit's meta is not read */
             const int32_t* rp = a.rice_params + (u0 + c) * a.params_stride;
             int cnt = 0;
             for (int k = tid; k < m.n_parts; k += NT) cnt += rp[k] > 14 ? 1 : 0;
@@ -375,7 +468,9 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
         for (int c = 0; c < C; ++c) {
             const flacmi_unit_meta& m = a.meta[u0 + c];
             sub_start[c] = s;
-            s += sub_prefix_bits(m, a.sample_size, a.q) + (uint32_t)sub_residual_bits(m, cnt14[c]);
+            const int kind = sub_kind_of<FB>(a, u0 + c);
+            s += kind ? sub_raw_bits(kind, unit_len(a, u0 + c), a.sample_size)
+                      : sub_prefix_bits(m, a.sample_size, a.q) + (uint32_t)sub_residual_bits(m, cnt14[c]);
         }
         sub_start[C] = s;
     }
@@ -402,9 +497,29 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
         const int64_t u = u0 + c;
         const flacmi_unit_meta& m = a.meta[u];
         const int n = unit_len(a, u);
+        const uint32_t s0 = sub_start[c];
+        if (const int kind = sub_kind_of<FB>(a, u)) {
+            /* CONSTANT / VERBATIM (encoder.py:559-578): the header byte, then 1 or n samples as
+             * ss-bit fields, 8 per thread a tile (a tile is at most 64 Kbit, half a window).  No
+             * unary part and no partition header; the window advance and the CRC are the Rice
+             * path's.  Uniform branch: kind is per unit. */
+            const int cnt = kind == FLACMI_SUB_CONSTANT ? 1 : n;
+            const uint64_t smask = (1ull << ss) - 1;
+            for (int t0 = 0; t0 < cnt; t0 += 8 * NT) {
+                const int t1 = t0 + 8 * NT < cnt ? t0 + 8 * NT : cnt;
+                segment(s0 + 8u + (uint32_t)t1 * ss, [&]() {
+                    if (t0 == 0 && tid == 0) win_or(win, wb, s0, (uint64_t)(kind == FLACMI_SUB_CONSTANT ? 0 : 2), 8);
+                    for (int i = t0 + 8 * tid; i < t1 && i < t0 + 8 * tid + 8; ++i) {
+                        const int64_t x = a.sample_bytes == 2 ? (int64_t)((const int16_t*)a.samples)[u * a.stride + i]
+                                                              : (int64_t)((const int32_t*)a.samples)[u * a.stride + i];
+                        win_or(win, wb, s0 + 8u + (uint32_t)i * ss, (uint64_t)x & smask, ss);
+                    }
+                });
+            }
+            continue;
+        }
         const int order = m.order, ncoefs = m.ncoefs, method = m.coding_method;
         const bool lpc = m.kind == FLACMI_KIND_LPC;
-        const uint32_t s0 = sub_start[c];
         const uint32_t pre = sub_prefix_bits(m, ss, q);
         /* subframe header, warm-up, LPC fields, residual header: field t per thread */
         const int nfields = 1 + order + (lpc ? 2 + ncoefs : 0) + 2;
@@ -609,8 +724,8 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
 
 /* General frame writer: every frame (pack_split = 0), or, after k_pack32, the frames it
  * listed (grid-stride over the list; an empty list costs one short launch). */
-template <typename ZT>
-__global__ __launch_bounds__(kPackThreads) void k_pack(FrameArgs a) {
+template <typename ZT, bool FB>
+__device__ __forceinline__ void pack_frames(const FrameArgs& a) {
     if (a.offsets[a.n_frames] > a.capacity) {
         if (blockIdx.x == 0 && threadIdx.x == 0)
             a.status[0] = (FLACMI_SITE_FRAME_SIZE << 16) | FLACMI_STATUS_FRAME_TOO_LARGE;
@@ -618,10 +733,15 @@ __global__ __launch_bounds__(kPackThreads) void k_pack(FrameArgs a) {
     }
     const int64_t cnt = a.pack_split ? (int64_t)*a.slow_count : (int64_t)blockIdx.x + 1;
     for (int64_t idx = blockIdx.x; idx < cnt; idx += gridDim.x) { /* one call site: inlined once */
-        pack_frame<ZT>(a, a.pack_split ? a.slow_list[idx] : idx);
+        pack_frame<ZT, FB>(a, a.pack_split ? a.slow_list[idx] : idx);
         __syncthreads(); /* LDS reuse by the next frame */
     }
 }
+template <typename ZT>
+__global__ __launch_bounds__(kPackThreads) void k_pack(FrameArgs a) { pack_frames<ZT, false>(a); }
+/* the fallback mode's build: CONSTANT / VERBATIM subframes from a.sub_kind */
+template <typename ZT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_fb(FrameArgs a) { pack_frames<ZT, true>(a); }
 
 /* ====================================================================================
  * k_pack32: the frame writer for frames that fit one LDS window (32-bit residuals).
@@ -651,7 +771,7 @@ __device__ __forceinline__ void or_bits(uint32_t* win, uint32_t P, uint32_t val,
  * in waves a SIMD.  A 3072-word window (14.3 KB of LDS) lets 10 workgroups share a CU, so
  * the floor of 7 waves (72 VGPRs, no spills) is reachable; the 16 KB window capped it at 8
  * workgroups, 6 waves a SIMD for 192-thread groups. */
-template <int MAXC, int WW, int WPE>
+template <int MAXC, int WW, int WPE, bool FB = false> /* FB: hands frames with escaped units to k_pack_fb */
 __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_pack32(FrameArgs a) {
     __shared__ uint32_t win[WW];
     __shared__ __align__(16) uint16_t ct[4 * 256];
@@ -675,7 +795,7 @@ __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(WP
     }
     if (a.offsets[a.n_frames] > a.capacity) return; /* k_pack reports it */
     if (a.status[f] != 0) return;
-    if (!pack32_frame_ok(a, f, WW)) { /* k_pack writes it */
+    if (!pack32_frame_ok<FB>(a, f, WW)) { /* k_pack writes it */
         if (threadIdx.x == 0) a.slow_list[atomicAdd(a.slow_count, 1ull)] = f;
         return;
     }
@@ -992,9 +1112,11 @@ __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(WP
  * (the rest go to k_pack by list).
  * ==================================================================================== */
 
+template <bool FB>
 __device__ __forceinline__ bool packw_frame_ok(const FrameArgs& a, int64_t f) {
     for (int c = 0; c < a.channels; ++c) {
         const int64_t u = f * a.channels + c;
+        if (sub_kind_of<FB>(a, u) != 0) return false; /* CONSTANT / VERBATIM: k_pack alone writes them */
         if ((unit_len(a, u) >> a.meta[u].part_order) < 8) return false;
     }
     return true;
@@ -1005,7 +1127,7 @@ __device__ __forceinline__ uint32_t crc_fold_word(uint32_t c, uint32_t w, const 
            (uint32_t)ct[256 + ((w >> 8) & 0xFF)] ^ (uint32_t)ct[w & 0xFF];
 }
 
-template <int MAXC, int NT, int RW> /* NT: the launch's threads; RW: ring words */
+template <int MAXC, int NT, int RW, bool FB> /* NT: the launch's threads; RW: ring words; FB: the fallback mode's build */
 __device__ __forceinline__ void packw_frame(const FrameArgs& a) {
     constexpr uint32_t RM = RW - 1;
     constexpr int CH = 2 * NT;                    /* words leaving the ring together */
@@ -1024,7 +1146,7 @@ __device__ __forceinline__ void packw_frame(const FrameArgs& a) {
     const int64_t f = blockIdx.x;
     if (a.offsets[a.n_frames] > a.capacity) return; /* k_pack reports it */
     if (a.status[f] != 0) return;
-    if (!packw_frame_ok(a, f)) { /* k_pack writes it */
+    if (!packw_frame_ok<FB>(a, f)) { /* k_pack writes it */
         if (tid == 0) a.slow_list[atomicAdd(a.slow_count, 1ull)] = f;
         return;
     }
@@ -1349,34 +1471,66 @@ __device__ __forceinline__ void packw_frame(const FrameArgs& a) {
  * 5.08.  k_packw_redo_test's MAXC = 4 (knob 3) gives 2048-value tiles, about 1400 ring words for 24-bit frames,
  * for the tests of the redo of a tile that overruns the ring. */
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_packw(FrameArgs a) {
-    packw_frame<1, 64, 1024>(a);
+    packw_frame<1, 64, 1024, false>(a);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
+void k_packw_fb(FrameArgs a) {
+    packw_frame<1, 64, 1024, true>(a);
 }
 __global__ __launch_bounds__(64) void k_packw_redo_test(FrameArgs a) { /* knob 3 (no occupancy floor) */
-    packw_frame<4, 64, 1024>(a);
+    packw_frame<4, 64, 1024, false>(a);
+}
+__global__ __launch_bounds__(64)
+void k_packw_redo_test_fb(FrameArgs a) {
+    packw_frame<4, 64, 1024, true>(a);
 }
 /* A/B builds: 256 threads on a 16 KB ring (the first default), 128 threads on an 8 KB ring */
 __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_packw256(FrameArgs a) {
-    packw_frame<1, kPackThreads, kWinWords>(a);
+    packw_frame<1, kPackThreads, kWinWords, false>(a);
+}
+__global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(6, 8)))
+void k_packw256_fb(FrameArgs a) {
+    packw_frame<1, kPackThreads, kWinWords, true>(a);
 }
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_packw128(FrameArgs a) {
-    packw_frame<1, 128, 2048>(a);
+    packw_frame<1, 128, 2048, false>(a);
+}
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8)))
+void k_packw128_fb(FrameArgs a) {
+    packw_frame<1, 128, 2048, true>(a);
 }
 /* samples of <= 16 bits: a 2 KB ring (5.2 KB of LDS: 24 workgroups a CU, the VGPR limit,
  * instead of 21).  A 512-value tile fits it above the < 128 waiting words up to 24 bits a
  * value; 16-bit residuals stay far below.  c2 frames 8.01 -> 7.35 ms same box (c3's 24-bit
  * frames only 5.02 -> 4.93, with tiles near the limit: they keep the 4 KB ring). */
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_packw2k(FrameArgs a) {
-    packw_frame<1, 64, 512>(a);
+    packw_frame<1, 64, 512, false>(a);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 8)))
+void k_packw2k_fb(FrameArgs a) {
+    packw_frame<1, 64, 512, true>(a);
 }
 /* knob 3 for samples of <= 16 bits: the 2 KB ring with 2048-value tiles (about 900 ring words
  * at 14 bits a value), so ordinary 16-bit frames overrun the ring that ships several times each */
 __global__ __launch_bounds__(64) void k_packw2k_redo_test(FrameArgs a) {
-    packw_frame<4, 64, 512>(a);
+    packw_frame<4, 64, 512, false>(a);
+}
+__global__ __launch_bounds__(64)
+void k_packw2k_redo_test_fb(FrameArgs a) {
+    packw_frame<4, 64, 512, true>(a);
 }
 
 hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_frame_sizes, dim3((unsigned)((a.n_frames + 3) / 4)), dim3(256), 0, s, a);
+    const dim3 frames4((unsigned)((a.n_frames + 3) / 4));
+    if (a.sub_kind) { /* fallback mode: one more launch, on the stream between the analysis and the sizes */
+        hipLaunchKernelGGL(k_sub_kinds, dim3((unsigned)((a.n_units + 3) / 4)), dim3(256), 0, s, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_frame_sizes_fb, frames4, dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(k_frame_sizes, frames4, dim3(256), 0, s, a);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int64_t n = a.n_frames;
@@ -1389,15 +1543,33 @@ hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s) 
 
 int64_t frame_scan_blocks(int64_t n_frames) { return (n_frames + kScanBlock - 1) / kScanBlock; }
 
+/* kernel K, or with the fallback mode on its _fb build */
+#define LAUNCH_FB(K, grid, threads, args)                                      \
+    do {                                                                       \
+        if (fb) hipLaunchKernelGGL(K##_fb, grid, threads, 0, s, args);         \
+        else hipLaunchKernelGGL(K, grid, threads, 0, s, args);                 \
+    } while (0)
+#define LAUNCH_PACK(ZT, grid, threads, args)                                   \
+    do {                                                                       \
+        if (fb) hipLaunchKernelGGL(k_pack_fb<ZT>, grid, threads, 0, s, args);  \
+        else hipLaunchKernelGGL(k_pack<ZT>, grid, threads, 0, s, args);        \
+    } while (0)
+#define LAUNCH_PACK32(MAXC, WW, WPE)                                                       \
+    do {                                                                                   \
+        if (fb) hipLaunchKernelGGL((k_pack32<MAXC, WW, WPE, true>), g, t, 0, s, b);       \
+        else hipLaunchKernelGGL((k_pack32<MAXC, WW, WPE>), g, t, 0, s, b);                \
+    } while (0)
+
 hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
+    const bool fb = a.sub_kind != nullptr;
     /* workgroup: 8-value chunks in as few full tiles of <= 256 threads as possible */
     const int nch = (a.block_len + 7) / 8;
     const int tiles = (nch + kPackThreads - 1) / kPackThreads;
     int nt = 64 * ((nch + 64 * tiles - 1) / (64 * tiles));
     nt = nt < 64 ? 64 : nt;
     if (a.residual_bytes == 8) {
-        hipLaunchKernelGGL(k_pack<uint64_t>, dim3((unsigned)a.n_frames), dim3(nt), 0, s, a);
+        LAUNCH_PACK(uint64_t, dim3((unsigned)a.n_frames), dim3(nt), a);
         return hipGetLastError();
     }
     FrameArgs b = a;
@@ -1430,16 +1602,16 @@ hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
         hipError_t e0 = hipMemsetAsync(b.slow_count, 0, sizeof(unsigned long long), s);
         if (e0 != hipSuccess) return e0;
         const dim3 g((unsigned)a.n_frames);
-        if (pack_generic == 3 && a.sample_size <= 16) hipLaunchKernelGGL(k_packw2k_redo_test, g, dim3(64), 0, s, b);
-        else if (pack_generic == 3) hipLaunchKernelGGL(k_packw_redo_test, g, dim3(64), 0, s, b);
-        else if (pack_generic == 6) hipLaunchKernelGGL(k_packw256, g, dim3(kPackThreads), 0, s, b);
-        else if (pack_generic == 8) hipLaunchKernelGGL(k_packw128, g, dim3(128), 0, s, b);
-        else if (a.sample_size <= 16) hipLaunchKernelGGL(k_packw2k, g, dim3(64), 0, s, b);
-        else hipLaunchKernelGGL(k_packw, g, dim3(64), 0, s, b);
+        if (pack_generic == 3 && a.sample_size <= 16) LAUNCH_FB(k_packw2k_redo_test, g, dim3(64), b);
+        else if (pack_generic == 3) LAUNCH_FB(k_packw_redo_test, g, dim3(64), b);
+        else if (pack_generic == 6) LAUNCH_FB(k_packw256, g, dim3(kPackThreads), b);
+        else if (pack_generic == 8) LAUNCH_FB(k_packw128, g, dim3(128), b);
+        else if (a.sample_size <= 16) LAUNCH_FB(k_packw2k, g, dim3(64), b);
+        else LAUNCH_FB(k_packw, g, dim3(64), b);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         const int64_t grid = a.n_frames < 4096 ? a.n_frames : 4096;
-        hipLaunchKernelGGL(k_pack<uint32_t>, dim3((unsigned)grid), dim3(nt), 0, s, b);
+        LAUNCH_PACK(uint32_t, dim3((unsigned)grid), dim3(nt), b);
         return hipGetLastError();
     }
     b.pack_split = !wide && vec_ok && !no_pack32;
@@ -1453,20 +1625,23 @@ hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
         const int64_t verb = (int64_t)a.block_len * a.sample_size * a.channels / 8 + 64;
         const bool small = verb + verb / 4 <= 4LL * kWinSmall && pack_generic != 7;
         if (small) {
-            if (cpt <= 2) hipLaunchKernelGGL((k_pack32<2, kWinSmall, 7>), g, t, 0, s, b);
-            else if (cpt == 3) hipLaunchKernelGGL((k_pack32<3, kWinSmall, 7>), g, t, 0, s, b);
-            else hipLaunchKernelGGL((k_pack32<kMaxC, kWinSmall, 5>), g, t, 0, s, b);
+            if (cpt <= 2) LAUNCH_PACK32(2, kWinSmall, 7);
+            else if (cpt == 3) LAUNCH_PACK32(3, kWinSmall, 7);
+            else LAUNCH_PACK32(kMaxC, kWinSmall, 5);
         } else {
-            if (cpt <= 2) hipLaunchKernelGGL((k_pack32<2, kWinWords, 1>), g, t, 0, s, b);
-            else if (cpt == 3) hipLaunchKernelGGL((k_pack32<3, kWinWords, 1>), g, t, 0, s, b);
-            else hipLaunchKernelGGL((k_pack32<kMaxC, kWinWords, 1>), g, t, 0, s, b);
+            if (cpt <= 2) LAUNCH_PACK32(2, kWinWords, 1);
+            else if (cpt == 3) LAUNCH_PACK32(3, kWinWords, 1);
+            else LAUNCH_PACK32(kMaxC, kWinWords, 1);
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     const int64_t grid = b.pack_split ? (a.n_frames < 4096 ? a.n_frames : 4096) : a.n_frames;
-    hipLaunchKernelGGL(k_pack<uint32_t>, dim3((unsigned)grid), dim3(nt), 0, s, b);
+    LAUNCH_PACK(uint32_t, dim3((unsigned)grid), dim3(nt), b);
     return hipGetLastError();
 }
+#undef LAUNCH_FB
+#undef LAUNCH_PACK
+#undef LAUNCH_PACK32
 
 }  // namespace flacmi

@@ -186,7 +186,7 @@ def put_frame_header(header: FrameHeader) -> Put:
 def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
            samples: Iterator[list], parameters: EncoderParameters, *, device: int = 0,
            devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 2048,
-           fixed_only: bool = False) -> Iterator[bytes]:
+           fixed_only: bool = False, fallback: bool = False) -> Iterator[bytes]:
     """flac/encoder.py:48-165 on the GPU: the per-channel analysis (k_lpc, k_resid) and
     the frame writer (k_frame.hip: Rice packing, headers, CRC-8/16), streamed through
     flacmi_encode_pipeline.  Only the stream header (magic + STREAMINFO) is written here.
@@ -195,7 +195,12 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
     batches go round-robin to one worker per entry and the frames come back in block
     order, byte-identical to one device.  fixed_only=True selects fixed predictors only
     (BASELINE config 5); the reference has no such mode (its -l 0 raises ValueError, which
-    the default mode reproduces)."""
+    the default mode reproduces).  fallback=True: a subframe the reference cannot write
+    (digital silence, a constant or linear block, a Rice partition of mean below 1, ...) or
+    writes larger than raw becomes a CONSTANT or VERBATIM subframe instead of raising
+    (include/flacmi.h FLACMI_FRAME_FALLBACK: the reference's own unused writers,
+    encoder.py:323-328 and :559-578, in place of the TODO at :104-125).  STREAMINFO is
+    unchanged; the frame-level failures still raise."""
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, frames, parameters)
@@ -214,12 +219,12 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
         if pending:
             yield index, functools.partial(_planar, pending, channels, n)
 
-    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size)
+    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback)
 
 
 def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameters: EncoderParameters, *,
                   frames: Optional[int] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
-                  blocks_per_batch: int = 0, fixed_only: bool = False) -> Iterator[bytes]:
+                  blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False) -> Iterator[bytes]:
     """encode() over planar PCM (int [channels][frames], e.g. from ingest.read_wav): the
     same bytes as encode(sample_rate, sample_size, channels, frames, <the frames of pcm>,
     parameters), without building a Python list per frame.  Blocks are cut straight into
@@ -240,12 +245,12 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
         for b0 in range(0, nb, bpb):
             yield b0, functools.partial(planar_blocks, pcm, n, b0, bpb)
 
-    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size)
+    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback)
 
 
 def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, device: int = 0,
                devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 0,
-               fixed_only: bool = False) -> Iterator[bytes]:
+               fixed_only: bool = False, fallback: bool = False) -> Iterator[bytes]:
     """The reference CLI's encode action (flac/__main__.py:58-109) on a WAV file, streamed:
     the stream header first, then frames batch by batch (ingest.iter_wav_pcm), so the host
     holds a bounded number of batches of PCM.  A reader failure (the reference's IndexError
@@ -265,7 +270,7 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
             yield b0, functools.partial(planar_blocks, pcm, n)
 
     # sessions are opened after the first batch is read: a reader failure needs no device
-    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, C, info.sample_width * 8)
+    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, C, info.sample_width * 8, fallback)
 
 
 def _stream_header(sample_rate, sample_size, channels, frames, parameters):
@@ -314,7 +319,8 @@ class _Session:
             buf = self.stage[slot] = self.az.host_array((max(nbytes, 1),), np.uint8)
         return buf[:nbytes].view(dtype).reshape(shape)
 
-    def encode(self, rows, bits, tail_len, n_tail, params, n, channels, sample_size, first_frame):
+    def encode(self, rows, bits, tail_len, n_tail, params, n, channels, sample_size, first_frame,
+               fallback: bool = False):
         """-> (frame bytes, offsets, status) of one batch (host copies: the buffers are reused)."""
         cap = int(rows.shape[0] * (n * rows.itemsize * 1.25 + 256)) + (1 << 20)
         while True:
@@ -325,7 +331,7 @@ class _Session:
                 data, offsets, status, _ = self.az.encode_pipeline(
                     rows, params, n, tail_len, n_tail, sample_bits=bits, channels=channels,
                     sample_size=sample_size, first_frame=first_frame, units_per_batch=_SUB_UNITS,
-                    out=self.out)
+                    out=self.out, fallback=fallback)
             except FlacmiError as e:
                 if e.code == abi.E_NOMEM:
                     cap = 2 * max(cap, self.out.size)
@@ -379,7 +385,7 @@ def _release(sessions) -> None:
         s.close()
 
 
-def _drive(batches, sessions, params, n, channels, sample_size) -> Iterator[bytes]:
+def _drive(batches, sessions, params, n, channels, sample_size, fallback=False) -> Iterator[bytes]:
     """batches yields (first_block, cut) with cut(alloc=...) -> (rows, bits, tail_len,
     n_tail_units); batch i goes to sessions[i % D].  Frames are yielded in block order; a
     frame the reference would fail on raises its exception after the frames before it, and
@@ -413,7 +419,7 @@ def _drive(batches, sessions, params, n, channels, sample_size) -> Iterator[byte
                 failure = e
                 break
             queue.append(s.pool.submit(s.encode, rows, bits, tail_len, n_tail, params, n, channels, sample_size,
-                                       first_block))
+                                       first_block, fallback))
             i += 1
         while queue:
             yield from _frames(*queue.popleft().result())

@@ -43,8 +43,10 @@ extern "C" {
 
 /* 2: in the default (pruning) mode meta.lpc_order / meta.lpc_sum of a unit whose LPC
       candidates provably lose read FLACMI_LPC_PRUNED, and stats word 80 no longer folds
-      lpc_sum (round 3); version 1 callers read exact LPC fields there */
-#define FLACMI_ABI_VERSION 2
+      lpc_sum (round 3); version 1 callers read exact LPC fields there
+   3: flacmi_frame_params.reserved0 carries the frame flags (FLACMI_FRAME_FALLBACK) and a value
+      with unknown bits is refused; version 2 callers passed 0 there and see no change */
+#define FLACMI_ABI_VERSION 3
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
                                         code); analysis returns FLACMI_E_UNSUPPORTED where a block's
@@ -230,14 +232,47 @@ int flacmi_analyze_host(flacmi_ctx* ctx, const flacmi_batch* batch,
  * the same bytes on the device: frame f of a batch holds the units
  * [f*channels, (f+1)*channels) (one subframe per channel, in channel order); the last
  * frame may be short (the batch's tail units).  Frames are byte-aligned and packed back
- * to back in `out` at frame_offsets[f] .. frame_offsets[f+1]. */
+ * to back in `out` at frame_offsets[f] .. frame_offsets[f+1].
+ *
+ * Fallback subframes (FLACMI_FRAME_FALLBACK, off by default; with it off every byte and
+ * status is the reference's).  The reference raises on much real audio (digital silence, a
+ * constant or linear block, a Rice partition whose mean zig-zag value is below 1) and never
+ * compares a subframe with its raw size: the TODO in encode() (encoder.py:104-125) wants
+ * verbatim subframes and "a reliable way of determining the size" of a subframe.  The mode
+ * replaces that TODO with the reference's own writers that nothing calls:
+ * encode_subframe_verbatim (:323-328) and the CONSTANT / VERBATIM cases of _put_subframe_type
+ * with _put_subframe_verbatim (:559-578); the size is the exact bit count the frame writer
+ * already computes.  A unit (one channel of one block, n samples, stream sample size ss) is
+ * escaped when
+ *   - its analysis status is a reference exception (ZeroDivisionError, AssertionError,
+ *     ValueError, OverflowError), or
+ *   - it is an LPC subframe and the writer's precision assertion (encoder.py:619) would raise, or
+ *   - its status is 0 and its exact subframe size is strictly greater than 8 + n * ss bits.
+ * An escaped unit whose n samples are all equal is written as CONSTANT (header 0 000000 0, the
+ * value in ss bits: 8 + ss bits), any other as VERBATIM (header 0 000001 0, every sample in ss
+ * bits, two's complement truncated as warm-up samples are: 8 + n * ss bits).  Not escaped, so
+ * failing the frame as before: FLACMI_STATUS_RESIDUAL_WIDE (the caller's 8-byte redo still
+ * happens), a block size or frame number that cannot be coded, FLACMI_STATUS_FRAME_TOO_LARGE
+ * and the output capacity. */
+enum flacmi_frame_flags {
+    FLACMI_FRAME_FALLBACK = 1,
+};
+/* per-unit decision of the fallback mode (sub_kind[u]) */
+enum flacmi_sub_kind {
+    FLACMI_SUB_ANALYSED = 0, /* the FIXED / LPC subframe of the analysis */
+    FLACMI_SUB_CONSTANT = 1,
+    FLACMI_SUB_VERBATIM = 2,
+};
 typedef struct flacmi_frame_params {
     int32_t channels;        /* units per frame, 1..8 (encode()'s channels) */
     int32_t sample_size;     /* bits per warm-up sample in the stream (encode()'s sample_size), 1..32 */
     int32_t qlp_precision;   /* SubframeLPC.precision (EncoderParameters.qlp_precision) */
-    int32_t reserved0;
+    int32_t reserved0;       /* enum flacmi_frame_flags bits (the name predates them); any other bit: FLACMI_E_INVALID */
     int64_t first_frame;     /* coded number of the batch's first frame (block index, encoder.py:97) */
-    int64_t reserved[2];
+    int64_t reserved[2];     /* reserved[0]: with FLACMI_FRAME_FALLBACK, for the *_device entry points, a device
+                                pointer to int32_t sub_kind[n_units] (flacmi_sub_kind) that
+                                flacmi_frame_sizes_device writes and flacmi_pack_frames_device reads;
+                                flacmi_encode_host / flacmi_encode_pipeline keep their own and ignore it */
 } flacmi_frame_params;
 
 /* Frame sizes and their exclusive prefix sums (device pointers, enqueued on `stream`).
