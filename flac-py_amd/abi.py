@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 3  # include/flacmi.h FLACMI_ABI_VERSION
+ABI_VERSION = 4  # include/flacmi.h FLACMI_ABI_VERSION
 MAX_LPC_ORDER = 32
 MAX_BLOCK = 65535
 MAX_RICE_ORDER = 15
@@ -74,6 +74,8 @@ FLAG_TIERS_ONLY = 2  # params.reserved[1]: prune with the partial-sum tiers alon
 LPC_PRUNED = -1          # meta.lpc_order / lpc_sum of a unit whose LPC candidates were pruned
 FRAME_FALLBACK = 1       # flacmi_frame_params.reserved0 (flacmi_frame_flags): CONSTANT / VERBATIM fallback subframes
 SUB_ANALYSED, SUB_CONSTANT, SUB_VERBATIM = 0, 1, 2  # flacmi_sub_kind: sub_kind[u] of the fallback mode
+STEREO_OFF, STEREO_BEST = 0, 1  # flacmi_frame_params.reserved[1] (flacmi_stereo_mode): stereo decorrelation
+CHANNELS_L_R, CHANNELS_L_S, CHANNELS_S_R, CHANNELS_M_S = 1, 8, 9, 10  # a stereo frame's channel assignment code
 
 
 class Params(C.Structure):
@@ -292,6 +294,8 @@ SIGNATURES = {
     "flacmi_encode_host": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Params), C.POINTER(FrameParams),
                                      C.c_void_p, C.c_void_p]),
     "flacmi_encode_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "flacmi_stereo_rows_device": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_int64, C.c_void_p]),
     "flacmi_encode_pipeline": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Params), C.POINTER(FrameParams),
                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.POINTER(EncodeTiming)]),

@@ -33,13 +33,16 @@ def make_params(max_lpc_order: int, qlp_precision: int, rice_min: int, rice_max:
 
 
 def frame_params(channels: int, sample_size: int, qlp_precision: int, first_frame: int = 0,
-                 fallback: bool = False, sub_kind_ptr: int = 0) -> abi.FrameParams:
+                 fallback: bool = False, sub_kind_ptr: int = 0, stereo: bool = False) -> abi.FrameParams:
     """fallback: FLACMI_FRAME_FALLBACK (a unit the reference cannot write, or writes larger than
     raw, becomes a CONSTANT / VERBATIM subframe); sub_kind_ptr: the device int32 [n_units] array
-    the *_device entry points then need (the host entry points keep their own)."""
+    the *_device entry points then need (the host entry points keep their own).  stereo:
+    FLACMI_STEREO_BEST (each two-channel frame takes the smallest of L_R, L_S, S_R, M_S; the host
+    entry points only)."""
     fp = abi.FrameParams()
     fp.reserved0 = abi.FRAME_FALLBACK if fallback else 0
     fp.reserved[0] = sub_kind_ptr
+    fp.reserved[1] = abi.STEREO_BEST if stereo else abi.STEREO_OFF
     fp.channels = channels
     fp.sample_size = sample_size
     fp.qlp_precision = qlp_precision
@@ -215,9 +218,10 @@ class Analyzer:
     # ------------------------------------------------------------------------------
     def encode_frames(self, samples: np.ndarray, params: abi.Params, block_len: int, tail_len: int = 0,
                       n_tail_units: int = 0, sample_bits: int = 16, channels: int = 1,
-                      sample_size: int = 16, first_frame: int = 0, fallback: bool = False):
+                      sample_size: int = 16, first_frame: int = 0, fallback: bool = False,
+                      stereo: bool = False):
         """Host rows in -> (frame bytes, frame offsets [n_frames + 1], frame status [n_frames]).
-        fallback: see frame_params.
+        fallback, stereo: see frame_params.
 
         Row f*channels + c is channel c of frame f.  A frame whose status is non-zero
         (the reference's exception, (site << 16) | status) has no bytes."""
@@ -234,7 +238,7 @@ class Analyzer:
         b.block_len = block_len
         b.tail_len = tail_len
         b.n_tail_units = n_tail_units
-        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback)
+        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback, stereo=stereo)
         n_frames = n_units // channels if channels else 0
         offsets = np.zeros(n_frames + 1, dtype=np.int64)
         status = np.zeros(max(n_frames, 1), dtype=np.int32)
@@ -248,7 +252,7 @@ class Analyzer:
     def encode_pipeline(self, samples: np.ndarray, params: abi.Params, block_len: int, tail_len: int = 0,
                         n_tail_units: int = 0, sample_bits: int = 16, channels: int = 1, sample_size: int = 16,
                         first_frame: int = 0, units_per_batch: int = 8192, capacity: int = 0,
-                        out: np.ndarray = None, fallback: bool = False):
+                        out: np.ndarray = None, fallback: bool = False, stereo: bool = False):
         """encode_frames through flacmi_encode_pipeline: host rows in (any row stride), the
         batch streamed through the device in sub-batches of units_per_batch units with the
         PCIe copies overlapping the kernels.  `out` (optional, uint8): the caller's frame
@@ -271,7 +275,7 @@ class Analyzer:
         b.block_len = block_len
         b.tail_len = tail_len
         b.n_tail_units = n_tail_units
-        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback)
+        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback, stereo=stereo)
         n_frames = n_units // channels if channels else 0
         offsets = np.zeros(n_frames + 1, dtype=np.int64)
         status = np.zeros(max(n_frames, 1), dtype=np.int32)
@@ -332,6 +336,14 @@ class Analyzer:
                                                  params_stride, residual_ptr, residual_bytes, residual_stride,
                                                  offsets_ptr, status_ptr, out_ptr, capacity, stream),
               "flacmi_pack_frames_device")
+
+    def stereo_rows_device(self, lr: abi.Batch, mid_ptr: int, mid_stride: int, side_ptr: int, side_stride: int,
+                           stream: int = 0) -> None:
+        """flacmi_stereo_rows_device: mid = (L + R) >> 1 rows (lr's element type) and side = L - R
+        rows (int32) of a two-channel device batch (rows 2f, 2f + 1 = left, right of frame f)."""
+        check(self.lib.flacmi_stereo_rows_device(self.ctx, C.byref(lr), mid_ptr, mid_stride, side_ptr, side_stride,
+                                                 stream),
+              "flacmi_stereo_rows_device")
 
     # ------------------------------------------------------------------------------
     # decoder verifier (include/flacmi.h flacmi_decode_frames_device)

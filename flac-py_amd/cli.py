@@ -5,7 +5,7 @@ frame writer through the streaming pipeline (encoder.encode_wav); --devices spre
 batches over several GPUs.
 
     python -m flac_amd encode infile.wav outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
-                                                       [--correct-reader] [--fixed-only] [--fallback]
+                                                       [--correct-reader] [--fixed-only] [--fallback] [--stereo]
                                                        [--device N | --devices N,M,...]
 
     python -m flac_amd decode infile.flac outfile.wav [--device N] [--check-crc]
@@ -45,6 +45,9 @@ def make_argument_parser():
     enc.add_argument("--fallback", action="store_true",
                      help="write a subframe the reference cannot write (digital silence, ...) or writes larger "
                           "than raw as CONSTANT / VERBATIM instead of stopping at its frame")
+    enc.add_argument("--stereo", action="store_true",
+                     help="stereo decorrelation (two-channel input): every frame takes the smallest of the "
+                          "left/right, left/side, side/right and mid/side channel assignments")
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
@@ -71,7 +74,8 @@ def cmd_encode(args) -> None:
     t0 = timer()
     with args.outfile.open("wb") as f:
         for bs in encode_wav(args.infile, parameters, quirk=not args.correct_reader, device=args.device,
-                             devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback):
+                             devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback,
+                             stereo=args.stereo):
             f.write(bs)
     print(f"Encoding completed in {timer() - t0:.6g} seconds")
 

@@ -165,6 +165,7 @@ struct flacmi_ctx {
     uint16_t* d_crc = nullptr;  /* CRC-16 slice tables [4][256] + power tables [28][512] */
     DevBuf scan, h_offsets, h_status, h_frames, dec, slow;
     DevBuf h_subkind;           /* flacmi_encode_host's sub_kind array (FLACMI_FRAME_FALLBACK) */
+    DevBuf h_side, h_choice;    /* flacmi_encode_host's side rows and per-frame choice (FLACMI_STEREO_BEST) */
     DevBuf idx, sd_data, sd_table, sd_meta, sd_rows, sd_pcm; /* frame index workspace; flacmi_decode_stream_host's buffers */
     int64_t frames_bytes = 0;   /* bytes of the last flacmi_encode_host call */
     static constexpr int kRing = 64;
@@ -313,7 +314,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     for (auto& kv : ctx->windows) (void)hipFree(kv.second);
     for (DevBuf* b : {&ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
-                      &ctx->h_frames, &ctx->h_subkind})
+                      &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice})
         if (b->p) (void)hipFree(b->p);
     if (ctx->d_log2thr) (void)hipFree(ctx->d_log2thr);
     if (ctx->d_sintab) (void)hipFree(ctx->d_sintab);
@@ -764,6 +765,10 @@ static int validate_frames(const flacmi_batch* b, const flacmi_frame_params* fp,
     if (fp->first_frame < 0) return fail(FLACMI_E_INVALID, "first_frame must be >= 0");
     if (fp->reserved0 & ~FLACMI_FRAME_FALLBACK)
         return fail(FLACMI_E_INVALID, "unknown frame flag bits %#x (reserved0)", (unsigned)fp->reserved0);
+    if (fp->reserved[1] != FLACMI_STEREO_OFF && fp->reserved[1] != FLACMI_STEREO_BEST)
+        return fail(FLACMI_E_INVALID, "unknown stereo mode %lld (reserved[1])", (long long)fp->reserved[1]);
+    if (fp->reserved[1] == FLACMI_STEREO_BEST && (fp->channels != 2 || fp->sample_size > 31))
+        return fail(FLACMI_E_INVALID, "the stereo mode (reserved[1]) needs channels == 2 and sample_size <= 31");
     if (b->n_units % fp->channels != 0) return fail(FLACMI_E_INVALID, "n_units must be a multiple of channels");
     if (b->n_tail_units != 0 && b->n_tail_units != fp->channels)
         return fail(FLACMI_E_INVALID, "the short last frame must hold exactly `channels` tail units");
@@ -805,11 +810,77 @@ static int caller_sub_kind(const flacmi_frame_params* fp, FrameArgs& a) {
 }
 
 /* the same for the host entry points: an array of their own (a context buffer, or one per
- * pipeline slot) */
+ * pipeline slot); in the stereo mode (a.choice set before this) over the 4 n_frames candidates */
 static int own_sub_kind(const flacmi_frame_params* fp, DevBuf& buf, FrameArgs& a) {
     if (!(fp->reserved0 & FLACMI_FRAME_FALLBACK)) return 0;
-    if (int rc = ensure_buf(buf, sizeof(int32_t) * (size_t)a.n_units)) return rc;
+    if (int rc = ensure_buf(buf, sizeof(int32_t) * (size_t)a.n_units * (a.choice ? 2 : 1))) return rc;
     a.sub_kind = (int32_t*)buf.p;
+    return 0;
+}
+
+/* ---- stereo mode (FLACMI_STEREO_BEST) at the host entry points --------------------------
+ * A sub-batch of nu = 2 F caller units has 4 F candidate units (frame_bits.h): the analysis
+ * outputs hold 2 nu units, the sample buffer nu + F rows (the mid rows behind the caller's, same
+ * pitch) and the side rows live in a buffer of their own (int32, their own pitch). */
+static bool stereo_on(const flacmi_frame_params* fp) { return fp->reserved[1] == FLACMI_STEREO_BEST; }
+static size_t stereo_out_units(const flacmi_frame_params* fp, size_t nu) { return stereo_on(fp) ? 2 * nu : nu; }
+static size_t stereo_sample_rows(const flacmi_frame_params* fp, size_t nu) { return stereo_on(fp) ? nu + nu / 2 : nu; }
+static const void* stereo_mid(const flacmi_batch& db) {
+    return (const char*)db.samples + (size_t)db.n_units * db.unit_stride * db.sample_bytes;
+}
+
+/* the *_device entry points' caller owns a layout of 2 units a frame */
+static int no_stereo(const flacmi_frame_params* fp) {
+    if (fp->reserved[1] != FLACMI_STEREO_OFF)
+        return fail(FLACMI_E_INVALID, "the stereo mode (reserved[1]) is honoured by flacmi_encode_host and "
+                                      "flacmi_encode_pipeline only");
+    return 0;
+}
+
+/* k_stereo_rows, then three analyses into the one set of outputs `o`: the caller's 2 F units of
+ * db (device rows), the F mid units and the F side units (an int32 batch, one bit wider); two
+ * tail units become one tail mid unit and one tail side unit */
+static int stereo_analyze(flacmi_ctx* ctx, const flacmi_batch& db, const flacmi_params* params,
+                          const flacmi_outputs& o, DevBuf& side, hipStream_t s, bool allow_overlap) {
+    const int64_t F = db.n_units / 2;
+    const int64_t side_stride = row_pitch(db.block_len, 4);
+    if (int rc = ensure_buf(side, (size_t)F * side_stride * sizeof(int32_t))) return rc;
+    HIP_TRY(launch_stereo_rows(db.samples, db.sample_bytes, db.unit_stride, F, db.block_len, db.tail_len,
+                               db.n_tail_units != 0, const_cast<void*>(stereo_mid(db)), db.unit_stride, (int32_t*)side.p,
+                               side_stride, s));
+    flacmi_batch bm = db;
+    bm.samples = stereo_mid(db);
+    bm.n_units = F;
+    bm.n_tail_units = db.n_tail_units ? 1 : 0;
+    flacmi_batch bs = bm;
+    bs.samples = side.p;
+    bs.sample_bytes = 4;
+    bs.sample_bits = db.sample_bits + 1;
+    bs.unit_stride = side_stride;
+    const flacmi_batch* batches[3] = {&db, &bm, &bs};
+    const int64_t unit0[3] = {0, 2 * F, 3 * F};
+    for (int i = 0; i < 3; ++i) {
+        flacmi_outputs oi = o;
+        oi.meta = o.meta + unit0[i];
+        oi.rice_params = o.rice_params + unit0[i] * o.params_stride;
+        oi.residual = (char*)o.residual + (size_t)unit0[i] * o.residual_stride * o.residual_bytes;
+        if (int rc = validate(batches[i], params, &oi)) return rc;
+        if (int rc = analyze_device_impl(ctx, batches[i], params, &oi, s, allow_overlap)) return rc;
+    }
+    return 0;
+}
+
+/* the frame writer's view of it: the choice array (one per context or pipeline slot), the mid and
+ * side rows; before own_sub_kind */
+static int stereo_args(const flacmi_frame_params* fp, const flacmi_batch& db, DevBuf& side, DevBuf& choice,
+                       FrameArgs& a) {
+    if (!stereo_on(fp)) return 0;
+    if (int rc = ensure_buf(choice, sizeof(StereoChoice) * (size_t)a.n_frames)) return rc;
+    a.choice = (StereoChoice*)choice.p;
+    a.mid = stereo_mid(db);
+    a.mid_stride = db.unit_stride;
+    a.side = (const int32_t*)side.p;
+    a.side_stride = row_pitch(db.block_len, 4);
     return 0;
 }
 
@@ -837,6 +908,7 @@ int flacmi_frame_sizes_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
     if (!ctx) return fail(FLACMI_E_INVALID, "null context");
     int64_t nf = 0;
     if (int rc = validate_frames(batch, fp, &nf)) return rc;
+    if (int rc = no_stereo(fp)) return rc;
     if (!meta || !rice_params || !frame_offsets || !frame_status) return fail(FLACMI_E_INVALID, "null buffer");
     if (int rc = set_device(ctx)) return rc;
     if (nf == 0) {
@@ -856,6 +928,7 @@ int flacmi_pack_frames_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
     if (!ctx) return fail(FLACMI_E_INVALID, "null context");
     int64_t nf = 0;
     if (int rc = validate_frames(batch, fp, &nf)) return rc;
+    if (int rc = no_stereo(fp)) return rc;
     if (!meta || !rice_params || !residual || !frame_offsets || !frame_status || (!out && out_capacity > 0))
         return fail(FLACMI_E_INVALID, "null buffer");
     if (residual_bytes != 4 && residual_bytes != 8) return fail(FLACMI_E_INVALID, "residual_bytes must be 4 or 8");
@@ -874,6 +947,31 @@ int flacmi_pack_frames_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
     a.capacity = out_capacity;
     if (int rc = pack_lists(ctx, a)) return rc;
     HIP_TRY(launch_pack(a, (hipStream_t)stream));
+    return 0;
+}
+
+int flacmi_stereo_rows_device(flacmi_ctx* ctx, const flacmi_batch* lr, void* mid, int64_t mid_stride, int32_t* side,
+                              int64_t side_stride, void* stream) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
+    if (!lr || !mid || !side) return fail(FLACMI_E_INVALID, "null argument");
+    if (lr->sample_bytes != 2 && lr->sample_bytes != 4) return fail(FLACMI_E_INVALID, "sample_bytes must be 2 or 4");
+    if (lr->n_units < 0 || lr->n_units % 2 != 0) return fail(FLACMI_E_INVALID, "n_units must be even (left, right rows)");
+    if (lr->n_tail_units != 0 && (lr->n_tail_units != 2 || lr->n_units < 2))
+        return fail(FLACMI_E_INVALID, "the short last frame must hold exactly 2 tail units");
+    if (lr->block_len < 1 || lr->block_len > FLACMI_MAX_BLOCK) return fail(FLACMI_E_INVALID, "block_len out of range");
+    if (lr->n_tail_units > 0 && (lr->tail_len < 1 || lr->tail_len > lr->block_len))
+        return fail(FLACMI_E_INVALID, "tail_len out of range");
+    if (lr->n_units == 0) return 0;
+    if (!lr->samples) return fail(FLACMI_E_INVALID, "null argument");
+    if (lr->unit_stride < lr->block_len || mid_stride < lr->block_len || side_stride < lr->block_len)
+        return fail(FLACMI_E_INVALID, "a row pitch is below block_len");
+    if ((lr->unit_stride * lr->sample_bytes) % 16 != 0 || (mid_stride * lr->sample_bytes) % 16 != 0 ||
+        (side_stride * 4) % 16 != 0 || ((uintptr_t)lr->samples | (uintptr_t)mid | (uintptr_t)side) % 16 != 0)
+        return fail(FLACMI_E_INVALID, "rows must be 16-byte aligned and every pitch a multiple of 16 bytes");
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(launch_stereo_rows(lr->samples, lr->sample_bytes, lr->unit_stride, lr->n_units / 2, lr->block_len,
+                               lr->tail_len, lr->n_tail_units != 0, mid, mid_stride, side, side_stride,
+                               (hipStream_t)stream));
     return 0;
 }
 
@@ -1370,11 +1468,13 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
     }
     if (int rc = set_device(ctx)) return rc;
     const size_t nu = (size_t)batch->n_units;
+    const bool stereo = stereo_on(fp);
+    const size_t nou = stereo_out_units(fp, nu); /* units of the analysis outputs */
     const int64_t sstride = row_pitch(batch->block_len, batch->sample_bytes);
     const int64_t pstride = (1LL << (params->rice_max > 0 ? params->rice_max : 0)) + 1;
-    if (int rc = ensure_buf(ctx->h_samples, nu * sstride * batch->sample_bytes)) return rc;
-    if (int rc = ensure_buf(ctx->h_meta, nu * sizeof(flacmi_unit_meta))) return rc;
-    if (int rc = ensure_buf(ctx->h_params, nu * pstride * sizeof(int32_t))) return rc;
+    if (int rc = ensure_buf(ctx->h_samples, stereo_sample_rows(fp, nu) * sstride * batch->sample_bytes)) return rc;
+    if (int rc = ensure_buf(ctx->h_meta, nou * sizeof(flacmi_unit_meta))) return rc;
+    if (int rc = ensure_buf(ctx->h_params, nou * pstride * sizeof(int32_t))) return rc;
     if (int rc = ensure_buf(ctx->h_offsets, sizeof(int64_t) * (size_t)(nf + 1))) return rc;
     if (int rc = ensure_buf(ctx->h_status, sizeof(int32_t) * (size_t)nf)) return rc;
     flacmi_batch db = *batch;
@@ -1385,7 +1485,7 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
                              hipMemcpyHostToDevice, ctx->stream));
     for (int rbytes = 4;; rbytes = 8) {
         const int64_t rstride = ((batch->block_len * rbytes + 15) / 16) * 16 / rbytes;
-        if (int rc = ensure_buf(ctx->h_residual, nu * rstride * rbytes)) return rc;
+        if (int rc = ensure_buf(ctx->h_residual, nou * rstride * rbytes)) return rc;
         flacmi_outputs o{};
         o.meta = (flacmi_unit_meta*)ctx->h_meta.p;
         o.rice_params = (int32_t*)ctx->h_params.p;
@@ -1393,9 +1493,14 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
         o.residual = ctx->h_residual.p;
         o.residual_bytes = rbytes;
         o.residual_stride = rstride;
-        if (int rc = validate(&db, params, &o)) return rc;
-        if (int rc = analyze_device_impl(ctx, &db, params, &o, ctx->stream)) return rc;
+        if (stereo) {
+            if (int rc = stereo_analyze(ctx, db, params, o, ctx->h_side, ctx->stream, true)) return rc;
+        } else {
+            if (int rc = validate(&db, params, &o)) return rc;
+            if (int rc = analyze_device_impl(ctx, &db, params, &o, ctx->stream)) return rc;
+        }
         FrameArgs a = frame_args(ctx, &db, fp, o.meta, o.rice_params, pstride, nf);
+        if (int rc = stereo_args(fp, db, ctx->h_side, ctx->h_choice, a)) return rc;
         if (int rc = own_sub_kind(fp, ctx->h_subkind, a)) return rc;
         if (int rc = frame_sizes_impl(ctx, a, (int64_t*)ctx->h_offsets.p, (int32_t*)ctx->h_status.p, ctx->stream))
             return rc;
@@ -1445,6 +1550,7 @@ constexpr int kEncSlots = 4; /* with 3 the host waited for the D2H of sub-batch 
 struct EncSlot {
     DevBuf samples, meta, params, residual, offsets, status, frames;
     DevBuf subkind;             /* sub_kind of the sub-batch's units (FLACMI_FRAME_FALLBACK) */
+    DevBuf side, choice;        /* side rows and per-frame choice of the sub-batch (FLACMI_STEREO_BEST) */
     int64_t* h_off = nullptr;   /* pinned, mapped: frame offsets of the sub-batch */
     int32_t* h_st = nullptr;    /* pinned, mapped: frame status */
     int64_t* d_off = nullptr;   /* their device-side addresses (k_export writes them) */
@@ -1474,7 +1580,7 @@ static void enc_free(EncState* es) {
         if (st) (void)hipStreamSynchronize(st);
     for (auto& sl : es->slot) {
         for (DevBuf* d : {&sl.samples, &sl.meta, &sl.params, &sl.residual, &sl.offsets, &sl.status, &sl.frames,
-                          &sl.subkind})
+                          &sl.subkind, &sl.side, &sl.choice})
             if (d->p) (void)hipFree(d->p);
         if (sl.h_off) (void)hipHostFree(sl.h_off);
         if (sl.h_st) (void)hipHostFree(sl.h_st);
@@ -1542,10 +1648,11 @@ static int enc_front(flacmi_ctx* ctx, EncSlot& sl, const flacmi_batch* whole, co
     const int64_t sstride = sl.dstride;
     const int64_t pstride = (1LL << (params->rice_max > 0 ? params->rice_max : 0)) + 1;
     const int64_t rstride = ((b.block_len * sl.rbytes + 15) / 16) * 16 / sl.rbytes;
-    if (int rc = ensure_buf(sl.samples, nu * sstride * b.sample_bytes)) return rc;
-    if (int rc = ensure_buf(sl.meta, nu * sizeof(flacmi_unit_meta))) return rc;
-    if (int rc = ensure_buf(sl.params, nu * pstride * sizeof(int32_t))) return rc;
-    if (int rc = ensure_buf(sl.residual, nu * rstride * sl.rbytes)) return rc;
+    const size_t nou = stereo_out_units(fp, nu); /* units of the analysis outputs */
+    if (int rc = ensure_buf(sl.samples, stereo_sample_rows(fp, nu) * sstride * b.sample_bytes)) return rc;
+    if (int rc = ensure_buf(sl.meta, nou * sizeof(flacmi_unit_meta))) return rc;
+    if (int rc = ensure_buf(sl.params, nou * pstride * sizeof(int32_t))) return rc;
+    if (int rc = ensure_buf(sl.residual, nou * rstride * sl.rbytes)) return rc;
     if (int rc = ensure_buf(sl.offsets, sizeof(int64_t) * (size_t)(sl.nf + 1))) return rc;
     if (int rc = ensure_buf(sl.status, sizeof(int32_t) * (size_t)sl.nf)) return rc;
     const uint8_t* src = (const uint8_t*)whole->samples + sl.first_unit * whole->unit_stride * b.sample_bytes;
@@ -1568,14 +1675,19 @@ static int enc_front(flacmi_ctx* ctx, EncSlot& sl, const flacmi_batch* whole, co
     o.residual = sl.residual.p;
     o.residual_bytes = sl.rbytes;
     o.residual_stride = rstride;
-    if (int rc = validate(&db, params, &o)) return rc;
     /* no chunk overlap inside the pipeline: its side stream is this pipeline's H2D stream,
        and the next sub-batch's copy would queue behind this one's k_lpc */
-    if (int rc = analyze_device_impl(ctx, &db, params, &o, cs, false)) return rc;
+    if (stereo_on(fp)) {
+        if (int rc = stereo_analyze(ctx, db, params, o, sl.side, cs, false)) return rc;
+    } else {
+        if (int rc = validate(&db, params, &o)) return rc;
+        if (int rc = analyze_device_impl(ctx, &db, params, &o, cs, false)) return rc;
+    }
     HIP_TRY(hipEventRecord(sl.e[2], cs));
     flacmi_frame_params f = *fp;
     f.first_frame = fp->first_frame + sl.first_unit / fp->channels;
     FrameArgs a = frame_args(ctx, &db, &f, o.meta, o.rice_params, pstride, sl.nf);
+    if (int rc = stereo_args(fp, db, sl.side, sl.choice, a)) return rc;
     if (int rc = own_sub_kind(fp, sl.subkind, a)) return rc;
     if (int rc = frame_sizes_impl(ctx, a, (int64_t*)sl.offsets.p, (int32_t*)sl.status.p, cs)) return rc;
     HIP_TRY(hipEventRecord(sl.e[3], cs));
@@ -1710,6 +1822,7 @@ extern "C" int flacmi_encode_pipeline(flacmi_ctx* ctx, const flacmi_batch* batch
             f.first_frame = fp->first_frame + f0;
             FrameArgs a = frame_args(ctx, &db, &f, (const flacmi_unit_meta*)sl.meta.p, (const int32_t*)sl.params.p,
                                      pstride, sl.nf);
+            if (int r = stereo_args(fp, db, sl.side, sl.choice, a)) return r; /* what enc_front's kernels wrote */
             if (int r = own_sub_kind(fp, sl.subkind, a)) return r; /* the array enc_front's k_sub_kinds wrote */
             a.residual = sl.residual.p;
             a.residual_bytes = sl.rbytes;

@@ -80,6 +80,13 @@ struct ResidArgs {
 /* internal unit status between the fast and the generic k_resid (never returned) */
 #define FLACMI_STATUS_RETRY 0x7e
 
+/* The stereo mode's verdict on one frame (k_stereo_choose, FLACMI_STEREO_BEST) */
+struct StereoChoice {
+    int32_t code;            /* channel assignment: 1 L_R, 8 L_S, 9 S_R, 10 M_S (header byte 3 >> 4) */
+    int32_t status;          /* non-zero: the frame fails with it (FLACMI_STATUS_RESIDUAL_WIDE on a candidate) */
+    int64_t unit[2];         /* the two subframes' candidate units (frame_bits.h: [0, 4 n_frames)) */
+};
+
 /* Frame writer (k_frame.hip): frame f = units [f*channels, (f+1)*channels). */
 struct FrameArgs {
     const void* samples;     /* warm-up samples come from the batch rows */
@@ -108,6 +115,14 @@ struct FrameArgs {
                                   3 neither (output invalid) */
     int32_t* sub_kind;         /* FLACMI_FRAME_FALLBACK: [n_units] flacmi_sub_kind, written by k_sub_kinds and
                                   read by k_frame_sizes and the writers; NULL: the mode is off */
+    /* FLACMI_STEREO_BEST (choice NULL: the mode is off).  meta, rice_params, the residual rows and
+       sub_kind then hold 4 n_frames candidate units: the caller's 2 n_frames, then the mid units,
+       then the side units (frame_bits.h); n_units stays the caller's count */
+    StereoChoice* choice;      /* [n_frames], written by k_stereo_choose, read by k_frame_sizes_st / k_pack_st */
+    const void* mid;           /* mid rows [n_frames], elements of sample_bytes */
+    int64_t mid_stride;
+    const int32_t* side;       /* side rows [n_frames], sample_size + 1 bits in int32 */
+    int64_t side_stride;
 };
 
 /* Decoder verifier (k_decode.hip): frame f = bytes [offsets[f], offsets[f+1]) of words. */
@@ -241,7 +256,18 @@ hipError_t launch_synth(void* dst, int32_t sample_bytes, int32_t bits, int64_t s
 hipError_t launch_stats(const flacmi_unit_meta* meta, int64_t n_units, int32_t block_len,
                         int32_t tail_len, int64_t n_tail_units, int64_t* stats, hipStream_t s);
 
-/* (a.sub_kind set: k_sub_kinds first,) frame sizes + exclusive scan into a.offsets; bsum:
+/* Stereo rows (k_stereo.hip): mid = (L + R) >> 1 in the input's element type and side = L - R in
+ * int32 for every frame's row pair 2f, 2f + 1 of lr; len samples a row (tail_len for the last
+ * frame when has_tail), elements from there to each output pitch zeroed.  Every row 16-byte
+ * aligned, every pitch a multiple of 16 bytes. */
+hipError_t launch_stereo_rows(const void* lr, int32_t sample_bytes, int64_t lr_stride, int64_t n_frames,
+                              int32_t block_len, int32_t tail_len, int32_t has_tail, void* mid, int64_t mid_stride,
+                              int32_t* side, int64_t side_stride, hipStream_t s);
+/* a.choice[f] from the four candidates' sizes (after k_sub_kinds in the fallback mode) */
+hipError_t launch_stereo_choose(const FrameArgs& a, hipStream_t s);
+
+/* (a.sub_kind set: k_sub_kinds first; a.choice set: over the 4 n_frames candidates, then
+ * k_stereo_choose,) frame sizes + exclusive scan into a.offsets; bsum:
  * frame_scan_blocks(n_frames) words */
 hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s);
 int64_t frame_scan_blocks(int64_t n_frames);

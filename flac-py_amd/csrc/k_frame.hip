@@ -22,6 +22,12 @@
  *                  the writers the reference never calls).  k_frame_sizes and k_pack take the
  *                  sizes and the subframes from its sub_kind array; the two fast writers
  *                  below hand such frames to k_pack by list.
+ *   the _st builds (stereo mode only, FLACMI_STEREO_BEST; k_stereo.hip makes the mid / side rows
+ *                  and chooses) of k_sub_kinds, k_frame_sizes and k_pack: a frame's two subframes
+ *                  are the candidate units a.choice[f] names, its header carries the chosen
+ *                  channel code, and a side unit's warm-up and raw samples are one bit wider.
+ *                  A stereo batch goes through k_pack_st for every frame; the fast writers below
+ *                  know no channel code and their code is unchanged.
  *   k_pack         one workgroup per frame.  Every field is OR-ed into an LDS window of
  *                  kWinWords 32-bit words at its exact bit position (positions from a
  *                  workgroup scan of per-value code lengths, 8 values per thread); a full
@@ -44,6 +50,7 @@
  * holds the frame's first byte, so window word k is output word (F >> 2) + wb + k.  The
  * window words hold bits MSB first; stores byte-swap them. */
 #include "device_common.h"
+#include "frame_bits.h"
 
 #include <cstdlib>
 
@@ -107,40 +114,24 @@ __device__ int frame_header(int64_t fno, int bs, uint8_t* h) {
     h[k++] = (uint8_t)c;
     return k;
 }
-
-__device__ __forceinline__ int unit_len(const FrameArgs& a, int64_t u) {
-    return u >= a.n_units - a.n_tail_units ? a.tail_len : a.block_len;
+/* The stereo mode's header: the frame's channel assignment code (common.py:200-211) in byte 3
+ * and the CRC-8 over the changed bytes.  frame_header itself stays as it is, so the writers that
+ * know no channel code are the code they were. */
+__device__ int frame_header_st(int64_t fno, int bs, int chan, uint8_t* h) {
+    const int k = frame_header(fno, bs, h);
+    if (k < 0) return k;
+    h[3] = (uint8_t)(chan << 4);
+    uint32_t c = 0;
+    for (int i = 0; i < k - 1; ++i) {
+        c ^= h[i];
+        for (int b = 0; b < 8; ++b) c = (c & 0x80) ? ((c << 1) ^ 0x07) & 0xFF : (c << 1) & 0xFF;
+    }
+    h[k - 1] = (uint8_t)c;
+    return k;
 }
 
-/* Bits of the subframe up to the first partition (encoder.py:553-627, :766-767). */
-__device__ __forceinline__ uint32_t sub_prefix_bits(const flacmi_unit_meta& m, int ss, int q) {
-    const bool lpc = m.kind == FLACMI_KIND_LPC;
-    return 8u + (uint32_t)m.order * (uint32_t)ss + (lpc ? 9u + (uint32_t)m.ncoefs * (uint32_t)q : 0u) + 6u;
-}
-
-/* Written residual bits (partition parameters + Rice codes) from the reference's estimate
- * rice_bits = sum_k [4 + (p_k > 14 ? 5 : 4) + data_k] (encoder.py:714-727):
- *   Rice4Bit: sum_k [4 + data_k]          = rice_bits - 4 n_parts
- *   Rice5Bit: sum_k [5 + data_k]          = rice_bits - 3 n_parts - #{p_k > 14} */
-__device__ __forceinline__ int64_t sub_residual_bits(const flacmi_unit_meta& m, int cnt14) {
-    return m.coding_method == 5 ? m.rice_bits - 3LL * m.n_parts - cnt14 : m.rice_bits - 4LL * m.n_parts;
-}
-
-/* What unit u is written as.  FB: the build of a kernel for the fallback mode (a.sub_kind
- * set); the builds for the mode off never look at the array, so they are the code they were
- * before the mode existed (an a.sub_kind test at run time cost k_packw2k 0.6% and
- * k_frame_sizes 5% on config 2's frames). */
-template <bool FB>
-__device__ __forceinline__ int sub_kind_of(const FrameArgs& a, int64_t u) {
-    if constexpr (FB) return a.sub_kind[u];
-    else return 0;
-}
-
-/* Bits of a CONSTANT / VERBATIM subframe (encoder.py:553-578): the header byte and one or n
- * samples of ss bits. */
-__device__ __forceinline__ uint32_t sub_raw_bits(int kind, int n, int ss) {
-    return 8u + (kind == FLACMI_SUB_CONSTANT ? 1u : (uint32_t)n) * (uint32_t)ss;
-}
+/* unit_len, sub_prefix_bits, sub_residual_bits, sub_kind_of, sub_raw_bits and the stereo mode's
+ * unit layout: frame_bits.h */
 
 /* ====================================================================================
  * k_sub_kinds: one wave per unit (fallback mode only)
@@ -152,12 +143,14 @@ __device__ __forceinline__ uint32_t sub_raw_bits(int kind, int n, int ss) {
  * or the LPC path has raised before), so only units with a nonzero status are scanned; a unit
  * escaped for its size or for the precision assertion is VERBATIM without reading its row.
  * ==================================================================================== */
-__global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) {
+template <bool ST> /* ST: over the stereo mode's 4 n_frames candidate units, the side units one bit wider */
+__device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
     const int lane = threadIdx.x & 63;
     const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (u >= a.n_units) return;
+    if (u >= (ST ? 4 * a.n_frames : a.n_units)) return;
     const flacmi_unit_meta& m = a.meta[u];
-    const int n = unit_len(a, u);
+    const int n = unit_len_of<ST>(a, u);
+    const int ss = unit_bits_of<ST>(a, u);
     const int st = m.status;
     bool esc;
     if (st != 0) {
@@ -172,8 +165,7 @@ __global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) {
             for (int k = lane; k < m.n_parts; k += 64) cnt += rp[k] > 14 ? 1 : 0;
             for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
         }
-        esc = (int64_t)sub_prefix_bits(m, a.sample_size, a.q) + sub_residual_bits(m, cnt) >
-              8 + (int64_t)n * a.sample_size;
+        esc = (int64_t)sub_prefix_bits(m, ss, a.q) + sub_residual_bits(m, cnt) > 8 + (int64_t)n * ss;
     }
     if (!esc || st == 0) {
         if (lane == 0) a.sub_kind[u] = esc ? FLACMI_SUB_VERBATIM : FLACMI_SUB_ANALYSED;
@@ -181,8 +173,8 @@ __global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) {
     }
     /* all samples equal to the first?  16-byte loads over the row's aligned middle, single
      * samples before and behind it; the wave stops at the first 1024-byte step with a mismatch */
-    const int sb = a.sample_bytes;
-    const uint8_t* row = (const uint8_t*)a.samples + u * a.stride * sb;
+    int sb;
+    const uint8_t* row = unit_row<ST>(a, u, sb);
     const int per = 16 / sb; /* samples a 16-byte load */
     int head = (int)((16 - ((uintptr_t)row & 15)) & 15) / sb;
     head = head < n ? head : n;
@@ -203,11 +195,13 @@ __global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) {
     const bool any_diff = __any(diff);
     if (lane == 0) a.sub_kind[u] = any_diff ? FLACMI_SUB_VERBATIM : FLACMI_SUB_CONSTANT;
 }
+__global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) { sub_kinds<false>(a); }
+__global__ __launch_bounds__(256) void k_sub_kinds_st(FrameArgs a) { sub_kinds<true>(a); }
 
 /* ====================================================================================
  * k_frame_sizes: one wave per frame
  * ==================================================================================== */
-template <bool FB>
+template <bool FB, bool ST = false> /* ST: the stereo mode's build (the frame's two units and code from a.choice) */
 __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
     const int lane = threadIdx.x & 63;
     const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -216,13 +210,18 @@ __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
     const int bs = unit_len(a, u0);
     uint8_t h[16];
     int st = 0;
-    const int hb = frame_header(a.first_frame + f, bs, h);
+    const int hb = frame_header(a.first_frame + f, bs, h); /* its length does not depend on the channel code */
     if (hb < 0) st = (FLACMI_SITE_CODED_NUMBER << 16) | FLACMI_STATUS_VALUE_ERROR;
+    if constexpr (ST)
+        if (st == 0) st = a.choice[f].status;
     int64_t bits = 0;
     for (int c = 0; c < a.channels && st == 0; ++c) {
-        const flacmi_unit_meta& m = a.meta[u0 + c];
-        if (const int kind = sub_kind_of<FB>(a, u0 + c)) { /* escaped: no status, no meta */
-            bits += sub_raw_bits(kind, bs, a.sample_size);
+        int64_t u = u0 + c;
+        if constexpr (ST) u = a.choice[f].unit[c];
+        const int ss = unit_bits_of<ST>(a, u);
+        const flacmi_unit_meta& m = a.meta[u];
+        if (const int kind = sub_kind_of<FB>(a, u)) { /* escaped: no status, no meta */
+            bits += sub_raw_bits(kind, bs, ss);
             continue;
         }
         if (m.status != 0) {
@@ -235,11 +234,11 @@ __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
         }
         int cnt = 0;
         if (m.coding_method == 5) {
-            const int32_t* rp = a.rice_params + (u0 + c) * a.params_stride;
+            const int32_t* rp = a.rice_params + u * a.params_stride;
             for (int k = lane; k < m.n_parts; k += 64) cnt += rp[k] > 14 ? 1 : 0;
             for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
         }
-        bits += (int64_t)sub_prefix_bits(m, a.sample_size, a.q) + sub_residual_bits(m, cnt);
+        bits += (int64_t)sub_prefix_bits(m, ss, a.q) + sub_residual_bits(m, cnt);
     }
     int64_t bytes = 0;
     if (st == 0) {
@@ -257,6 +256,8 @@ __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
 }
 __global__ __launch_bounds__(256) void k_frame_sizes(FrameArgs a) { frame_sizes<false>(a); }
 __global__ __launch_bounds__(256) void k_frame_sizes_fb(FrameArgs a) { frame_sizes<true>(a); }
+__global__ __launch_bounds__(256) void k_frame_sizes_st(FrameArgs a) { frame_sizes<false, true>(a); }
+__global__ __launch_bounds__(256) void k_frame_sizes_st_fb(FrameArgs a) { frame_sizes<true, true>(a); }
 
 /* ---- exclusive scan of frame sizes (in place on offsets[1..n]) ---------------------- */
 constexpr int kScanItems = 8;
@@ -432,7 +433,9 @@ __device__ __forceinline__ bool pack32_frame_ok(const FrameArgs& a, int64_t f, i
     return true;
 }
 
-template <typename ZT, bool FB>
+/* ST: the stereo mode's build (a.choice: the frame's channel code and its two candidate units,
+ * the side unit one bit wider) */
+template <typename ZT, bool FB, bool ST = false>
 __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) {
     __shared__ uint32_t win[kWinWords];
     __shared__ uint16_t ct[4 * 256];
@@ -446,15 +449,25 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
     const int64_t F = a.offsets[f], Fend = a.offsets[f + 1];
     const int64_t u0 = f * a.channels;
     const int C = a.channels;
+    /* channel c's unit */
+    auto unit_of = [&](int c) __attribute__((always_inline)) -> int64_t {
+        if constexpr (ST) return a.choice[f].unit[c];
+        else return u0 + c;
+    };
     for (int i = tid; i < 4 * 256; i += NT) ct[i] = a.crc_slice[i];
     for (int i = tid; i < kWinWords; i += NT) win[i] = 0;
     if (tid < 8) cnt14[tid] = 0;
-    if (tid == 0) hb_s = frame_header(a.first_frame + f, unit_len(a, u0), hdr);
+    if constexpr (ST) {
+        if (tid == 0) hb_s = frame_header_st(a.first_frame + f, unit_len(a, u0), a.choice[f].code, hdr);
+    } else {
+        if (tid == 0) hb_s = frame_header(a.first_frame + f, unit_len(a, u0), hdr);
+    }
     __syncthreads();
     for (int c = 0; c < C; ++c) {
-        const flacmi_unit_meta& m = a.meta[u0 + c];
-        if (sub_kind_of<FB>(a, u0 + c) == 0 && m.coding_method == 5) { /* an escaped unit's meta is not read */
-            const int32_t* rp = a.rice_params + (u0 + c) * a.params_stride;
+        const int64_t u = unit_of(c);
+        const flacmi_unit_meta& m = a.meta[u];
+        if (sub_kind_of<FB>(a, u) == 0 && m.coding_method == 5) { /* an escaped unit's meta is not read */
+            const int32_t* rp = a.rice_params + u * a.params_stride;
             int cnt = 0;
             for (int k = tid; k < m.n_parts; k += NT) cnt += rp[k] > 14 ? 1 : 0;
             if (cnt) atomicAdd(&cnt14[c], cnt);
@@ -466,11 +479,13 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
     if (tid == 0) {
         uint32_t s = A + 8u * (uint32_t)hb;
         for (int c = 0; c < C; ++c) {
-            const flacmi_unit_meta& m = a.meta[u0 + c];
+            const int64_t u = unit_of(c);
+            const flacmi_unit_meta& m = a.meta[u];
             sub_start[c] = s;
-            const int kind = sub_kind_of<FB>(a, u0 + c);
-            s += kind ? sub_raw_bits(kind, unit_len(a, u0 + c), a.sample_size)
-                      : sub_prefix_bits(m, a.sample_size, a.q) + (uint32_t)sub_residual_bits(m, cnt14[c]);
+            const int kind = sub_kind_of<FB>(a, u);
+            const int w = unit_bits_of<ST>(a, u);
+            s += kind ? sub_raw_bits(kind, unit_len_of<ST>(a, u), w)
+                      : sub_prefix_bits(m, w, a.q) + (uint32_t)sub_residual_bits(m, cnt14[c]);
         }
         sub_start[C] = s;
     }
@@ -492,11 +507,12 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
     segment(A + 8u * hb, [&]() {
         if (tid < hb) win_or(win, wb, A + 8u * tid, hdr[tid], 8);
     });
-    const int ss = a.sample_size, q = a.q;
+    const int q = a.q;
     for (int c = 0; c < C; ++c) {
-        const int64_t u = u0 + c;
+        const int64_t u = unit_of(c);
         const flacmi_unit_meta& m = a.meta[u];
-        const int n = unit_len(a, u);
+        const int n = unit_len_of<ST>(a, u);
+        const int ss = unit_bits_of<ST>(a, u);
         const uint32_t s0 = sub_start[c];
         if (const int kind = sub_kind_of<FB>(a, u)) {
             /* CONSTANT / VERBATIM (encoder.py:559-578): the header byte, then 1 or n samples as
@@ -510,8 +526,7 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
                 segment(s0 + 8u + (uint32_t)t1 * ss, [&]() {
                     if (t0 == 0 && tid == 0) win_or(win, wb, s0, (uint64_t)(kind == FLACMI_SUB_CONSTANT ? 0 : 2), 8);
                     for (int i = t0 + 8 * tid; i < t1 && i < t0 + 8 * tid + 8; ++i) {
-                        const int64_t x = a.sample_bytes == 2 ? (int64_t)((const int16_t*)a.samples)[u * a.stride + i]
-                                                              : (int64_t)((const int32_t*)a.samples)[u * a.stride + i];
+                        const int64_t x = unit_sample<ST>(a, u, i);
                         win_or(win, wb, s0 + 8u + (uint32_t)i * ss, (uint64_t)x & smask, ss);
                     }
                 });
@@ -534,8 +549,7 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
                     w = 8;
                 } else if (t <= order) {
                     const int j = t - 1;
-                    const int64_t x = a.sample_bytes == 2 ? (int64_t)((const int16_t*)a.samples)[u * a.stride + j]
-                                                          : (int64_t)((const int32_t*)a.samples)[u * a.stride + j];
+                    const int64_t x = unit_sample<ST>(a, u, j);
                     pos = s0 + 8 + (uint32_t)j * ss;
                     v = (uint64_t)x & (ss == 64 ? ~0ull : ((1ull << ss) - 1));
                     w = ss;
@@ -724,7 +738,7 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
 
 /* General frame writer: every frame (pack_split = 0), or, after k_pack32, the frames it
  * listed (grid-stride over the list; an empty list costs one short launch). */
-template <typename ZT, bool FB>
+template <typename ZT, bool FB, bool ST = false>
 __device__ __forceinline__ void pack_frames(const FrameArgs& a) {
     if (a.offsets[a.n_frames] > a.capacity) {
         if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -733,7 +747,7 @@ __device__ __forceinline__ void pack_frames(const FrameArgs& a) {
     }
     const int64_t cnt = a.pack_split ? (int64_t)*a.slow_count : (int64_t)blockIdx.x + 1;
     for (int64_t idx = blockIdx.x; idx < cnt; idx += gridDim.x) { /* one call site: inlined once */
-        pack_frame<ZT, FB>(a, a.pack_split ? a.slow_list[idx] : idx);
+        pack_frame<ZT, FB, ST>(a, a.pack_split ? a.slow_list[idx] : idx);
         __syncthreads(); /* LDS reuse by the next frame */
     }
 }
@@ -742,6 +756,11 @@ __global__ __launch_bounds__(kPackThreads) void k_pack(FrameArgs a) { pack_frame
 /* the fallback mode's build: CONSTANT / VERBATIM subframes from a.sub_kind */
 template <typename ZT>
 __global__ __launch_bounds__(kPackThreads) void k_pack_fb(FrameArgs a) { pack_frames<ZT, true>(a); }
+/* the stereo mode's builds (every frame of a stereo batch goes through them) */
+template <typename ZT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_st(FrameArgs a) { pack_frames<ZT, false, true>(a); }
+template <typename ZT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_st_fb(FrameArgs a) { pack_frames<ZT, true, true>(a); }
 
 /* ====================================================================================
  * k_pack32: the frame writer for frames that fit one LDS window (32-bit residuals).
@@ -1523,7 +1542,17 @@ void k_packw2k_redo_test_fb(FrameArgs a) {
 hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s) {
     if (a.n_frames <= 0) return hipSuccess;
     const dim3 frames4((unsigned)((a.n_frames + 3) / 4));
-    if (a.sub_kind) { /* fallback mode: one more launch, on the stream between the analysis and the sizes */
+    if (a.choice) { /* stereo mode: (the sub-kinds of all 4 n_frames candidates,) the choice, the sizes */
+        if (a.sub_kind) {
+            hipLaunchKernelGGL(k_sub_kinds_st, dim3((unsigned)a.n_frames), dim3(256), 0, s, a);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        hipError_t e = launch_stereo_choose(a, s);
+        if (e != hipSuccess) return e;
+        if (a.sub_kind) hipLaunchKernelGGL(k_frame_sizes_st_fb, frames4, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(k_frame_sizes_st, frames4, dim3(256), 0, s, a);
+    } else if (a.sub_kind) { /* fallback mode: one more launch, on the stream between the analysis and the sizes */
         hipLaunchKernelGGL(k_sub_kinds, dim3((unsigned)((a.n_units + 3) / 4)), dim3(256), 0, s, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -1568,6 +1597,17 @@ hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
     const int tiles = (nch + kPackThreads - 1) / kPackThreads;
     int nt = 64 * ((nch + 64 * tiles - 1) / (64 * tiles));
     nt = nt < 64 ? 64 : nt;
+    if (a.choice) { /* stereo mode: the general writer for every frame (the fast writers know no channel code) */
+        const dim3 g((unsigned)a.n_frames), t(nt);
+        if (a.residual_bytes == 8) {
+            if (fb) hipLaunchKernelGGL(k_pack_st_fb<uint64_t>, g, t, 0, s, a);
+            else hipLaunchKernelGGL(k_pack_st<uint64_t>, g, t, 0, s, a);
+        } else {
+            if (fb) hipLaunchKernelGGL(k_pack_st_fb<uint32_t>, g, t, 0, s, a);
+            else hipLaunchKernelGGL(k_pack_st<uint32_t>, g, t, 0, s, a);
+        }
+        return hipGetLastError();
+    }
     if (a.residual_bytes == 8) {
         LAUNCH_PACK(uint64_t, dim3((unsigned)a.n_frames), dim3(nt), a);
         return hipGetLastError();

@@ -186,7 +186,7 @@ def put_frame_header(header: FrameHeader) -> Put:
 def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
            samples: Iterator[list], parameters: EncoderParameters, *, device: int = 0,
            devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 2048,
-           fixed_only: bool = False, fallback: bool = False) -> Iterator[bytes]:
+           fixed_only: bool = False, fallback: bool = False, stereo: bool = False) -> Iterator[bytes]:
     """flac/encoder.py:48-165 on the GPU: the per-channel analysis (k_lpc, k_resid) and
     the frame writer (k_frame.hip: Rice packing, headers, CRC-8/16), streamed through
     flacmi_encode_pipeline.  Only the stream header (magic + STREAMINFO) is written here.
@@ -200,7 +200,12 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
     writes larger than raw becomes a CONSTANT or VERBATIM subframe instead of raising
     (include/flacmi.h FLACMI_FRAME_FALLBACK: the reference's own unused writers,
     encoder.py:323-328 and :559-578, in place of the TODO at :104-125).  STREAMINFO is
-    unchanged; the frame-level failures still raise."""
+    unchanged; the frame-level failures still raise.  stereo=True (two channels only): every
+    frame takes the smallest of the four stereo channel assignments L_R, L_S, S_R, M_S
+    (include/flacmi.h FLACMI_STEREO_BEST; the reference writes L_R always, encoder.py:95, and its
+    decoder reads all four); it composes with fallback, fixed_only and devices, and STREAMINFO
+    is unchanged."""
+    _check_stereo(stereo, channels)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, frames, parameters)
@@ -219,12 +224,14 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
         if pending:
             yield index, functools.partial(_planar, pending, channels, n)
 
-    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback)
+    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback,
+                      stereo)
 
 
 def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameters: EncoderParameters, *,
                   frames: Optional[int] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
-                  blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False) -> Iterator[bytes]:
+                  blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False,
+                  stereo: bool = False) -> Iterator[bytes]:
     """encode() over planar PCM (int [channels][frames], e.g. from ingest.read_wav): the
     same bytes as encode(sample_rate, sample_size, channels, frames, <the frames of pcm>,
     parameters), without building a Python list per frame.  Blocks are cut straight into
@@ -232,6 +239,7 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
     256 MB of samples) and streamed through flacmi_encode_pipeline; devices as encode()."""
     from .ingest import planar_blocks
     channels, total = pcm.shape
+    _check_stereo(stereo, channels)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, total if frames is None else frames,
@@ -245,12 +253,13 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
         for b0 in range(0, nb, bpb):
             yield b0, functools.partial(planar_blocks, pcm, n, b0, bpb)
 
-    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback)
+    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback,
+                      stereo)
 
 
 def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, device: int = 0,
                devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 0,
-               fixed_only: bool = False, fallback: bool = False) -> Iterator[bytes]:
+               fixed_only: bool = False, fallback: bool = False, stereo: bool = False) -> Iterator[bytes]:
     """The reference CLI's encode action (flac/__main__.py:58-109) on a WAV file, streamed:
     the stream header first, then frames batch by batch (ingest.iter_wav_pcm), so the host
     holds a bounded number of batches of PCM.  A reader failure (the reference's IndexError
@@ -258,6 +267,7 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
     of the batches before it, as the reference CLI has written them by then."""
     from .ingest import iter_wav_pcm, planar_blocks, wav_info
     info = wav_info(path)
+    _check_stereo(stereo, info.channels)
     if info.sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(info.sample_rate, info.sample_width * 8, info.channels, info.frames, parameters)
@@ -270,7 +280,14 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
             yield b0, functools.partial(planar_blocks, pcm, n)
 
     # sessions are opened after the first batch is read: a reader failure needs no device
-    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, C, info.sample_width * 8, fallback)
+    yield from _drive(batches(), lambda: _sessions(device, devices), params, n, C, info.sample_width * 8, fallback,
+                      stereo)
+
+
+def _check_stereo(stereo: bool, channels: int) -> None:
+    """stereo=True needs two channels; refused before any device work."""
+    if stereo and channels != 2:
+        raise ValueError(f"stereo decorrelation needs 2 channels, the input has {channels}")
 
 
 def _stream_header(sample_rate, sample_size, channels, frames, parameters):
@@ -320,7 +337,7 @@ class _Session:
         return buf[:nbytes].view(dtype).reshape(shape)
 
     def encode(self, rows, bits, tail_len, n_tail, params, n, channels, sample_size, first_frame,
-               fallback: bool = False):
+               fallback: bool = False, stereo: bool = False):
         """-> (frame bytes, offsets, status) of one batch (host copies: the buffers are reused)."""
         cap = int(rows.shape[0] * (n * rows.itemsize * 1.25 + 256)) + (1 << 20)
         while True:
@@ -331,7 +348,7 @@ class _Session:
                 data, offsets, status, _ = self.az.encode_pipeline(
                     rows, params, n, tail_len, n_tail, sample_bits=bits, channels=channels,
                     sample_size=sample_size, first_frame=first_frame, units_per_batch=_SUB_UNITS,
-                    out=self.out, fallback=fallback)
+                    out=self.out, fallback=fallback, stereo=stereo)
             except FlacmiError as e:
                 if e.code == abi.E_NOMEM:
                     cap = 2 * max(cap, self.out.size)
@@ -385,7 +402,7 @@ def _release(sessions) -> None:
         s.close()
 
 
-def _drive(batches, sessions, params, n, channels, sample_size, fallback=False) -> Iterator[bytes]:
+def _drive(batches, sessions, params, n, channels, sample_size, fallback=False, stereo=False) -> Iterator[bytes]:
     """batches yields (first_block, cut) with cut(alloc=...) -> (rows, bits, tail_len,
     n_tail_units); batch i goes to sessions[i % D].  Frames are yielded in block order; a
     frame the reference would fail on raises its exception after the frames before it, and
@@ -419,7 +436,7 @@ def _drive(batches, sessions, params, n, channels, sample_size, fallback=False) 
                 failure = e
                 break
             queue.append(s.pool.submit(s.encode, rows, bits, tail_len, n_tail, params, n, channels, sample_size,
-                                       first_block, fallback))
+                                       first_block, fallback, stereo))
             i += 1
         while queue:
             yield from _frames(*queue.popleft().result())

@@ -45,8 +45,11 @@ extern "C" {
       candidates provably lose read FLACMI_LPC_PRUNED, and stats word 80 no longer folds
       lpc_sum (round 3); version 1 callers read exact LPC fields there
    3: flacmi_frame_params.reserved0 carries the frame flags (FLACMI_FRAME_FALLBACK) and a value
-      with unknown bits is refused; version 2 callers passed 0 there and see no change */
-#define FLACMI_ABI_VERSION 3
+      with unknown bits is refused; version 2 callers passed 0 there and see no change
+   4: flacmi_frame_params.reserved[1] is the stereo mode (enum flacmi_stereo_mode) and any value
+      but 0 and 1 is refused; flacmi_stereo_rows_device is new; version 3 callers passed 0 there
+      and see no change */
+#define FLACMI_ABI_VERSION 4
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
                                         code); analysis returns FLACMI_E_UNSUPPORTED where a block's
@@ -253,7 +256,33 @@ int flacmi_analyze_host(flacmi_ctx* ctx, const flacmi_batch* batch,
  * bits, two's complement truncated as warm-up samples are: 8 + n * ss bits).  Not escaped, so
  * failing the frame as before: FLACMI_STATUS_RESIDUAL_WIDE (the caller's 8-byte redo still
  * happens), a block size or frame number that cannot be coded, FLACMI_STATUS_FRAME_TOO_LARGE
- * and the output capacity. */
+ * and the output capacity.
+ *
+ * Stereo decorrelation (FLACMI_STEREO_BEST in reserved[1], off by default; with it off every
+ * byte, status and launch is as without it).  encode() writes Channels.L_R for every frame
+ * (encoder.py:95; the reference's README: "Stereo decorrelation is not implemented yet"), while
+ * its decoder undoes all four stereo assignments (decoder.py:111-122, :431-451).  The mode is
+ * honoured by flacmi_encode_host and flacmi_encode_pipeline for channels == 2 and
+ * sample_size <= 31.  A frame of n samples with L = channel 0, R = channel 1 has four candidate
+ * signals: L and R (ss bits), M = (L + R) >> 1 (arithmetic shift; ss bits) and S = L - R
+ * (ss + 1 bits).  Each is analysed as a unit exactly as a channel holding those samples is (the
+ * reference's per-channel analysis never looks at the sample size): same parameters, pruning,
+ * status and site.  A candidate's size is the exact bit count the frame writer writes for its
+ * subframe, warm-up and raw samples at the candidate's own width w.  Without
+ * FLACMI_FRAME_FALLBACK a candidate is not eligible when its status is a reference exception or
+ * it is an LPC subframe and the precision assertion (encoder.py:619) would raise; with it an
+ * escaped candidate (the rule above, against 8 + n * w) counts its CONSTANT / VERBATIM size,
+ * 8 + w or 8 + n * w.  The assignments are walked in the order
+ *   L_R (channel code 1: subframes L, R), L_S (8: L, S), S_R (9: S, R), M_S (10: M, S)
+ * and the frame takes the first with the smallest sum of its two sizes among those whose two
+ * candidates are both eligible; its header carries that code and its side subframe is written
+ * at ss + 1 bits.  With no eligible assignment the frame fails with the status the L_R frame has
+ * without the mode.  FLACMI_STATUS_RESIDUAL_WIDE on any candidate fails the frame with that status
+ * (the redo with 8-byte residual rows still happens); the frame-level failures are unchanged. */
+enum flacmi_stereo_mode {
+    FLACMI_STEREO_OFF = 0,
+    FLACMI_STEREO_BEST = 1,
+};
 enum flacmi_frame_flags {
     FLACMI_FRAME_FALLBACK = 1,
 };
@@ -272,7 +301,11 @@ typedef struct flacmi_frame_params {
     int64_t reserved[2];     /* reserved[0]: with FLACMI_FRAME_FALLBACK, for the *_device entry points, a device
                                 pointer to int32_t sub_kind[n_units] (flacmi_sub_kind) that
                                 flacmi_frame_sizes_device writes and flacmi_pack_frames_device reads;
-                                flacmi_encode_host / flacmi_encode_pipeline keep their own and ignore it */
+                                flacmi_encode_host / flacmi_encode_pipeline keep their own and ignore it.
+                                reserved[1]: enum flacmi_stereo_mode, honoured by flacmi_encode_host and
+                                flacmi_encode_pipeline (channels == 2, sample_size <= 31); the *_device entry
+                                points, whose caller owns a 2-units-a-frame layout, refuse a non-zero mode;
+                                any other value: FLACMI_E_INVALID */
 } flacmi_frame_params;
 
 /* Frame sizes and their exclusive prefix sums (device pointers, enqueued on `stream`).
@@ -299,6 +332,17 @@ int flacmi_pack_frames_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
 int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_params* params,
                        const flacmi_frame_params* fp, int64_t* frame_offsets, int32_t* frame_status);
 int flacmi_encode_fetch(flacmi_ctx* ctx, uint8_t* out, int64_t bytes);
+
+/* The mid and side rows of a two-channel batch (the stereo mode's first step; device pointers,
+ * enqueued on `stream`): rows 2f and 2f + 1 of `lr` are the left and right channel of frame f
+ * (lr->n_units even; int16 or int32 rows; a short last frame has n_tail_units == 2).  mid row f
+ * receives (L + R) >> 1 (arithmetic shift, computed without the 33rd bit) in lr's element type
+ * at a pitch of mid_stride elements, side row f receives L - R as int32 at a pitch of
+ * side_stride elements (for 32-bit inputs the difference wraps; the stereo mode stops at 31).
+ * Elements from the frame's length up to each pitch are written as 0.  Every row must be 16-byte
+ * aligned, every pitch a multiple of 16 bytes and at least block_len elements. */
+int flacmi_stereo_rows_device(flacmi_ctx* ctx, const flacmi_batch* lr, void* mid, int64_t mid_stride,
+                              int32_t* side, int64_t side_stride, void* stream);
 
 /* Pipelined host encode (SURVEY §8d end-to-end; the reference's encode() loop plus its
  * writer, encoder.py:87-165, 765-806): host sample rows in, FLAC frame bytes out, the batch
