@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 4  # include/flacmi.h FLACMI_ABI_VERSION
+ABI_VERSION = 5  # include/flacmi.h FLACMI_ABI_VERSION
 MAX_LPC_ORDER = 32
 MAX_BLOCK = 65535
 MAX_RICE_ORDER = 15
@@ -71,6 +71,7 @@ KIND_FIXED = 0
 KIND_LPC = 1
 FLAG_ALL_CANDIDATES = 1  # params.reserved[1]: exact sums for every LPC candidate (no pruning)
 FLAG_TIERS_ONLY = 2  # params.reserved[1]: prune with the partial-sum tiers alone (diagnostic)
+FLAG_LPC_SIGN = 4  # params.reserved[1]: the corrected LPC predictor sign (negated Levinson coefficients)
 LPC_PRUNED = -1          # meta.lpc_order / lpc_sum of a unit whose LPC candidates were pruned
 FRAME_FALLBACK = 1       # flacmi_frame_params.reserved0 (flacmi_frame_flags): CONSTANT / VERBATIM fallback subframes
 SUB_ANALYSED, SUB_CONSTANT, SUB_VERBATIM = 0, 1, 2  # flacmi_sub_kind: sub_kind[u] of the fallback mode

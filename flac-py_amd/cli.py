@@ -6,6 +6,7 @@ batches over several GPUs.
 
     python -m flac_amd encode infile.wav outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
                                                        [--correct-reader] [--fixed-only] [--fallback] [--stereo]
+                                                       [--lpc-sign]
                                                        [--device N | --devices N,M,...]
 
     python -m flac_amd decode infile.flac outfile.wav [--device N] [--check-crc]
@@ -48,6 +49,9 @@ def make_argument_parser():
     enc.add_argument("--stereo", action="store_true",
                      help="stereo decorrelation (two-channel input): every frame takes the smallest of the "
                           "left/right, left/side, side/right and mid/side channel assignments")
+    enc.add_argument("--lpc-sign", action="store_true",
+                     help="corrected LPC predictor sign: the LPC candidates predict x and not -x (the "
+                          "reference's levinson_durbin returns the negated predictor)")
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
@@ -75,7 +79,7 @@ def cmd_encode(args) -> None:
     with args.outfile.open("wb") as f:
         for bs in encode_wav(args.infile, parameters, quirk=not args.correct_reader, device=args.device,
                              devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback,
-                             stereo=args.stereo):
+                             stereo=args.stereo, lpc_sign=args.lpc_sign):
             f.write(bs)
     print(f"Encoding completed in {timer() - t0:.6g} seconds")
 

@@ -393,6 +393,8 @@ static int validate(const flacmi_batch* b, const flacmi_params* p, const flacmi_
         return fail(FLACMI_E_INVALID, "RICE_ONLY predictor order (reserved[0]) must be 0..32");
     if (p->mode == FLACMI_MODE_LPC_ONLY && p->max_lpc_order < 1)
         return fail(FLACMI_E_INVALID, "LPC_ONLY needs max_lpc_order >= 1");
+    if ((p->reserved[1] & FLACMI_FLAG_LPC_SIGN) && (p->mode == FLACMI_MODE_FIXED_ONLY || p->mode == FLACMI_MODE_RICE_ONLY))
+        return fail(FLACMI_E_INVALID, "FLACMI_FLAG_LPC_SIGN needs FLACMI_MODE_REFERENCE or FLACMI_MODE_LPC_ONLY");
     if (p->mode != FLACMI_MODE_FIXED_ONLY && p->mode != FLACMI_MODE_RICE_ONLY && b->sample_bits + p->qlp_precision > 44)
         return fail(FLACMI_E_UNSUPPORTED,
                     "sample_bits + qlp_precision > 44: candidate residual sums may exceed int64 (see DESIGN.md)");
@@ -581,6 +583,7 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         a.n = k.n;
         a.L = L;
         a.q = p->qlp_precision;
+        a.lpc_sign = (p->reserved[1] & FLACMI_FLAG_LPC_SIGN) != 0;
         if (int rc = get_window(ctx, k.n, (double**)&a.window, &a.fuse_lo, &a.fuse_hi)) return rc;
         if (b->sample_bits > 26) a.fuse_lo = a.fuse_hi = 0; /* products must stay below 2^52 */
         a.log2thr = ctx->d_log2thr;
@@ -622,8 +625,10 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         a.retry2_list = rb + kSubWords + 4 + b->n_units + 64;
         a.sample_bits = b->sample_bits;
         a.stream = use_stream();
-        a.prune = p->mode == FLACMI_MODE_REFERENCE && !o->lpc_sums && !(p->reserved[1] & FLACMI_FLAG_ALL_CANDIDATES) &&
-                  prune_allowed();
+        /* every bound the kernels hold proves "LPC loses", the rare case once the predictor has
+         * its sign: FLACMI_FLAG_LPC_SIGN computes every candidate's exact sum */
+        a.prune = p->mode == FLACMI_MODE_REFERENCE && !o->lpc_sums &&
+                  !(p->reserved[1] & (FLACMI_FLAG_ALL_CANDIDATES | FLACMI_FLAG_LPC_SIGN)) && prune_allowed();
         a.sign_bound = !(p->reserved[1] & FLACMI_FLAG_TIERS_ONLY) && sign_bound_allowed();
         const bool wide = needs_wide(k.n, b->sample_bits, L, p->qlp_precision, p->mode);
         int path = (wide || o->residual_bytes == 8) ? 2 : (b->sample_bytes == 2 && p->qlp_precision <= 16) ? 0 : 1;

@@ -28,6 +28,7 @@ struct LpcArgs {
     const double* log2thr;   /* [PYM_LOG2_THR_N] floor(log2) thresholds */
     int32_t* rec;            /* [count][rec_words] LPC records (workspace) */
     int32_t rec_words;
+    int32_t lpc_sign;        /* FLACMI_FLAG_LPC_SIGN: quantise the negated Levinson coefficients */
     double* acf;             /* optional [count][33] */
     int32_t fuse_lo, fuse_hi; /* window[i] == 1.0 exactly for i in [fuse_lo, fuse_hi) and
                                  |x| < 2^26 (0, 0: no fused blocks), see k_lpc */

@@ -39,6 +39,7 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
     uint32_t negmask = 0;
     const double qmax = (double)((1LL << (q - 1)) - 1);
     const double qmin = -(double)(1LL << (q - 1));
+    const uint64_t sign = a.lpc_sign ? 1ull << 63 : 0;
     static_for<LMAX>([&](auto K_) {
         constexpr int k = K_;
         if (k < L && lst == ST_OK) {
@@ -91,7 +92,10 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
                         qsite = FLACMI_SITE_QUANT_SHIFT;
                     } else {
                         const bool neg = shift < 0;
-                        const double scale = pow2_exact(neg ? -shift : shift);
+                        /* FLACMI_FLAG_LPC_SIGN quantises -c[j]: (-c) * 2^s == c * (-2^s) exactly, so
+                         * the sign goes into the scale once per order (cm, shift and the status
+                         * sites depend on |c| alone): +-2^|shift|, pow2_exact with the sign bit */
+                        const double scale = pym::as_double(((uint64_t)(1023 + (neg ? -shift : shift)) << 52) | sign);
                         double e = 0.0;
 #pragma unroll
                         for (int j = 1; j <= LMAX; ++j) {

@@ -186,7 +186,8 @@ def put_frame_header(header: FrameHeader) -> Put:
 def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
            samples: Iterator[list], parameters: EncoderParameters, *, device: int = 0,
            devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 2048,
-           fixed_only: bool = False, fallback: bool = False, stereo: bool = False) -> Iterator[bytes]:
+           fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
+           lpc_sign: bool = False) -> Iterator[bytes]:
     """flac/encoder.py:48-165 on the GPU: the per-channel analysis (k_lpc, k_resid) and
     the frame writer (k_frame.hip: Rice packing, headers, CRC-8/16), streamed through
     flacmi_encode_pipeline.  Only the stream header (magic + STREAMINFO) is written here.
@@ -204,12 +205,16 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
     frame takes the smallest of the four stereo channel assignments L_R, L_S, S_R, M_S
     (include/flacmi.h FLACMI_STEREO_BEST; the reference writes L_R always, encoder.py:95, and its
     decoder reads all four); it composes with fallback, fixed_only and devices, and STREAMINFO
-    is unchanged."""
+    is unchanged.  lpc_sign=True: the LPC candidates use the predictor and not its negation, as if
+    the reference's levinson_durbin returned [-c for c in coefs[1:]] (include/flacmi.h
+    FLACMI_FLAG_LPC_SIGN); LPC subframes then win on most signals.  It composes with fallback,
+    stereo and devices; with fixed_only=True it raises ValueError."""
+    _check_lpc_sign(lpc_sign, fixed_only)
     _check_stereo(stereo, channels)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, frames, parameters)
-    params = _params(parameters, fixed_only)
+    params = _params(parameters, fixed_only, lpc_sign)
     n = parameters.block_size
 
     def batches():
@@ -231,7 +236,7 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
 def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameters: EncoderParameters, *,
                   frames: Optional[int] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
                   blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False,
-                  stereo: bool = False) -> Iterator[bytes]:
+                  stereo: bool = False, lpc_sign: bool = False) -> Iterator[bytes]:
     """encode() over planar PCM (int [channels][frames], e.g. from ingest.read_wav): the
     same bytes as encode(sample_rate, sample_size, channels, frames, <the frames of pcm>,
     parameters), without building a Python list per frame.  Blocks are cut straight into
@@ -239,12 +244,13 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
     256 MB of samples) and streamed through flacmi_encode_pipeline; devices as encode()."""
     from .ingest import planar_blocks
     channels, total = pcm.shape
+    _check_lpc_sign(lpc_sign, fixed_only)
     _check_stereo(stereo, channels)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, total if frames is None else frames,
                               parameters)
-    params = _params(parameters, fixed_only)
+    params = _params(parameters, fixed_only, lpc_sign)
     n = parameters.block_size
     nb = (total + n - 1) // n
     bpb = blocks_per_batch or _default_blocks(n, channels)
@@ -259,19 +265,21 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
 
 def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, device: int = 0,
                devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 0,
-               fixed_only: bool = False, fallback: bool = False, stereo: bool = False) -> Iterator[bytes]:
+               fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
+               lpc_sign: bool = False) -> Iterator[bytes]:
     """The reference CLI's encode action (flac/__main__.py:58-109) on a WAV file, streamed:
     the stream header first, then frames batch by batch (ingest.iter_wav_pcm), so the host
     holds a bounded number of batches of PCM.  A reader failure (the reference's IndexError
     on its byte grouping, encoder.py:102) is raised after the stream header and the frames
     of the batches before it, as the reference CLI has written them by then."""
     from .ingest import iter_wav_pcm, planar_blocks, wav_info
+    _check_lpc_sign(lpc_sign, fixed_only)
     info = wav_info(path)
     _check_stereo(stereo, info.channels)
     if info.sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(info.sample_rate, info.sample_width * 8, info.channels, info.frames, parameters)
-    params = _params(parameters, fixed_only)
+    params = _params(parameters, fixed_only, lpc_sign)
     n, C = parameters.block_size, info.channels
     bpb = blocks_per_batch or _default_blocks(n, C)
 
@@ -282,6 +290,12 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
     # sessions are opened after the first batch is read: a reader failure needs no device
     yield from _drive(batches(), lambda: _sessions(device, devices), params, n, C, info.sample_width * 8, fallback,
                       stereo)
+
+
+def _check_lpc_sign(lpc_sign: bool, fixed_only: bool) -> None:
+    """lpc_sign=True has no meaning without LPC candidates; refused before any device work."""
+    if lpc_sign and fixed_only:
+        raise ValueError("lpc_sign corrects the LPC candidates, fixed_only has none")
 
 
 def _check_stereo(stereo: bool, channels: int) -> None:
@@ -300,10 +314,11 @@ def _stream_header(sample_rate, sample_size, channels, frames, parameters):
         sample_size=sample_size, samples=frames, md5=bytes(16))).buffer
 
 
-def _params(parameters: EncoderParameters, fixed_only: bool) -> abi.Params:
+def _params(parameters: EncoderParameters, fixed_only: bool, lpc_sign: bool = False) -> abi.Params:
     rmin, rmax = _rice_range(parameters.rice_partition_order)
     mode = abi.MODE_FIXED_ONLY if fixed_only else abi.MODE_REFERENCE
-    return make_params(parameters.lpc_order.stop - 1, parameters.qlp_precision, rmin, rmax, mode)
+    return make_params(parameters.lpc_order.stop - 1, parameters.qlp_precision, rmin, rmax, mode,
+                       lpc_sign=lpc_sign)
 
 
 # ---------------------------------------------------------------------------------
@@ -487,12 +502,13 @@ def encode_subframe_fixed(samples: list):
             SubframeFixed(list(samples[:order]), residual))
 
 
-def encode_subframe_lpc(samples: list, lpc_order: range, precision: int):
-    """flac/encoder.py:362-420 -> (SubframeHeader, SubframeLPC)."""
+def encode_subframe_lpc(samples: list, lpc_order: range, precision: int, *, lpc_sign: bool = False):
+    """flac/encoder.py:362-420 -> (SubframeHeader, SubframeLPC).  lpc_sign=True: with the
+    corrected predictor sign (FLACMI_FLAG_LPC_SIGN)."""
     L = lpc_order.stop - 1
     if L < 1:
         raise ValueError("min() arg is an empty sequence")
-    out, m = _one(samples, make_params(L, precision, 0, -1, abi.MODE_LPC_ONLY))
+    out, m = _one(samples, make_params(L, precision, 0, -1, abi.MODE_LPC_ONLY, lpc_sign=lpc_sign))
     _raise_for(m)
     order = int(m["order"])
     off, ln = int(m["res_offset"]), int(m["res_len"])

@@ -48,8 +48,10 @@ extern "C" {
       with unknown bits is refused; version 2 callers passed 0 there and see no change
    4: flacmi_frame_params.reserved[1] is the stereo mode (enum flacmi_stereo_mode) and any value
       but 0 and 1 is refused; flacmi_stereo_rows_device is new; version 3 callers passed 0 there
-      and see no change */
-#define FLACMI_ABI_VERSION 4
+      and see no change
+   5: flacmi_params.reserved[1] takes FLACMI_FLAG_LPC_SIGN (the corrected LPC predictor sign, off by
+      default); version 4 callers never set bit 2 there and see no change */
+#define FLACMI_ABI_VERSION 5
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
                                         code); analysis returns FLACMI_E_UNSUPPORTED where a block's
@@ -136,13 +138,26 @@ enum flacmi_flags {
     /* diagnostic: prune with the partial-sum tiers alone (no sign-correlation bound), so a
      * test reaches the tier decisions on data the bound already settles */
     FLACMI_FLAG_TIERS_ONLY = 2,
+    /* the corrected LPC predictor sign: the analysis computes what the reference would if its
+     * levinson_durbin (encoder.py:453-479) ended with `return [-c for c in coefs[1:]]`, i.e. the
+     * predictor and not its negation.  The quantiser (encoder.py:482-534) runs on the negated
+     * floats (its clamp is asymmetric, so the result is not the negated default record);
+     * coef_max, the shift, every exception site, the ([], 0) negative-shift branch, the order
+     * choice, the fixed/LPC comparison with its tie, the Rice search and the writers are
+     * unchanged.  Honoured in FLACMI_MODE_REFERENCE and FLACMI_MODE_LPC_ONLY by every entry point
+     * that takes flacmi_params; with FIXED_ONLY or RICE_ONLY the call fails with
+     * FLACMI_E_INVALID.  The mode never prunes: meta.lpc_order / lpc_sum are exact,
+     * FLACMI_LPC_PRUNED never appears and meta.lpc_tiers is 0 (0x101, one exact pass, on the units
+     * k_resid_stream's list kernel takes, as with FLACMI_FLAG_ALL_CANDIDATES).  The reference decoder and
+     * flacmi_decode_* read the LPC subframes it writes as they are. */
+    FLACMI_FLAG_LPC_SIGN = 4,
 };
 
 /* meta.lpc_order and meta.lpc_sum of a unit whose LPC candidates were pruned: exact lower
  * bounds proved every candidate's sum(|r|) strictly above the best fixed sum, so the
  * reference's choice (encoder.py:135-157) is the fixed subframe and no tie is possible.
  * Everything the reference writes (kind, order, residual, Rice fields) is unaffected.  Runs
- * with outputs.lpc_sums or FLACMI_FLAG_ALL_CANDIDATES never prune. */
+ * with outputs.lpc_sums, FLACMI_FLAG_ALL_CANDIDATES or FLACMI_FLAG_LPC_SIGN never prune. */
 #define FLACMI_LPC_PRUNED (-1)
 
 /* One batch of units.  Samples are planar: unit u occupies
