@@ -161,6 +161,8 @@ struct flacmi_ctx {
     int32_t* d_sintab = nullptr;
     std::map<int, double*> windows;
     std::map<int, std::pair<int, int>> window_one; /* per n: [lo, hi) where the weight is 1.0 */
+    std::map<int, uint16_t*> chunk_weights;        /* per n: the energy bound's weight per 8-sample chunk */
+    DevBuf bound;                                  /* k_lpc's energy-bound words [units][2] */
     DevBuf rec, retry, h_samples, h_meta, h_params, h_residual, h_acf, h_fs, h_ls, h_recs;
     uint16_t* d_crc = nullptr;  /* CRC-16 slice tables [4][256] + power tables [28][512] */
     DevBuf scan, h_offsets, h_status, h_frames, dec, slow;
@@ -212,7 +214,7 @@ struct KnobDef {
     int dflt;
 };
 constexpr KnobDef kKnobs[kKnobCount] = {{"FLACMI_OVERLAP", -1}, {"FLACMI_MF8_GRID", 0}, {"FLACMI_STREAM_GENERIC", 0}, {"FLACMI_DECODE_GENERIC", 0},
-                                        {"FLACMI_PACK_GENERIC", 0}, {"FLACMI_DECODE_LPC", 1}};
+                                        {"FLACMI_PACK_GENERIC", 0}, {"FLACMI_DECODE_LPC", 1}, {"FLACMI_ENERGY_BOUND", 1}};
 std::atomic<int> g_knob[kKnobCount];
 std::once_flag g_knob_once;
 void knobs_init() {
@@ -312,7 +314,8 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     (void)hipDeviceSynchronize();
     enc_free(ctx->enc);
     for (auto& kv : ctx->windows) (void)hipFree(kv.second);
-    for (DevBuf* b : {&ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
+    for (auto& kv : ctx->chunk_weights) (void)hipFree(kv.second);
+    for (DevBuf* b : {&ctx->bound, &ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
                       &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice})
         if (b->p) (void)hipFree(b->p);
@@ -330,10 +333,37 @@ void flacmi_destroy(flacmi_ctx* ctx) {
 
 }  // extern "C"
 
-static int get_window(flacmi_ctx* ctx, int n, double** out, int* one_lo = nullptr, int* one_hi = nullptr) {
+/* The energy bound's two tables from the window's own weights.
+ * kappa_k = max |w_i - w_{i-k}| over k <= i <= n - 2, rounded up, for k = 1 .. kBoundLags.
+ * One weight per 8-sample chunk: floor(256 min w) over the chunk's samples, where sample
+ * n - 1 (it never enters the autocorrelation) and the samples below 16 (at most 12 of them
+ * are warm-up samples, which no candidate's sum holds) count as weight 0. */
+static void bound_tables(const std::vector<double>& w, int n, double* kappa, std::vector<uint16_t>& cw) {
+    for (int k = 1; k <= kBoundLags; ++k) {
+        double m = 0.0;
+        for (int i = k; i <= n - 2; ++i) m = std::max(m, fabs(w[i] - w[i - k]));
+        kappa[k - 1] = m * (1.0 + ldexp(1.0, -50));
+    }
+    cw.assign((size_t)(n + 7) / 8, 0);
+    for (int c = 2; 8 * c < n; ++c) {
+        double m = 1.0;
+        for (int i = 8 * c; i < 8 * c + 8; ++i) m = std::min(m, i < n - 1 ? w[i] : 0.0);
+        cw[c] = (uint16_t)floor(256.0 * m);
+    }
+}
+
+static int get_window(flacmi_ctx* ctx, int n, double** out, int* one_lo = nullptr, int* one_hi = nullptr,
+                      const uint16_t** chunk_weight = nullptr) {
     auto it = ctx->windows.find(n);
     if (it == ctx->windows.end()) {
         std::vector<double> w = tukey_window(n, kWindowPad);
+        std::vector<uint16_t> cw;
+        w.resize(w.size() + kBoundLags, 0.0); /* kappa_1 .. behind the zero pad */
+        bound_tables(w, n, w.data() + n + kWindowPad, cw);
+        uint16_t* dcw = nullptr;
+        HIP_TRY(hipMalloc(&dcw, sizeof(uint16_t) * cw.size()));
+        HIP_TRY(hipMemcpy(dcw, cw.data(), sizeof(uint16_t) * cw.size(), hipMemcpyHostToDevice));
+        ctx->chunk_weights[n] = dcw;
         double* d = nullptr;
         HIP_TRY(hipMalloc(&d, sizeof(double) * w.size()));
         HIP_TRY(hipMemcpy(d, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
@@ -359,6 +389,7 @@ static int get_window(flacmi_ctx* ctx, int n, double** out, int* one_lo = nullpt
     *out = it->second;
     if (one_lo) *one_lo = ctx->window_one[n].first;
     if (one_hi) *one_hi = ctx->window_one[n].second;
+    if (chunk_weight) *chunk_weight = ctx->chunk_weights[n];
     return 0;
 }
 
@@ -509,6 +540,14 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         if (int rc = ensure_buf(ctx->rec, sizeof(int32_t) * (size_t)rec_words * (size_t)(b->n_units > 0 ? b->n_units : 1)))
             return rc;
     }
+    /* the energy bound (k_lpc's words, k_resid_stream's pre-test): wherever the stream kernel may prune */
+    const int energy = debug_stop() >= 11 ? 0 : knob(kKnobEnergyBound); /* (the tier ablations time the tiers) */
+    const bool prune_call = p->mode == FLACMI_MODE_REFERENCE && !o->lpc_sums &&
+                            !(p->reserved[1] & (FLACMI_FLAG_ALL_CANDIDATES | FLACMI_FLAG_LPC_SIGN)) && prune_allowed();
+    const bool ebound = energy != 0 && prune_call && L >= 1 && L <= 12 && b->sample_bytes == 2 && p->qlp_precision <= 16;
+    if (ebound) {
+        if (int rc = ensure_buf(ctx->bound, sizeof(uint32_t) * 2 * (size_t)(b->n_units > 0 ? b->n_units : 1))) return rc;
+    }
     /* fast-kernel retry lists: 64 sub-list counters (k_resid_stream's batch kernel, 128 B apart),
      * a counter and one batch index per unit (plus 64 for the sub-lists' rounding), then the
      * second list through which k_resid_stream's list kernel hands units on */
@@ -585,6 +624,7 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         a.q = p->qlp_precision;
         a.lpc_sign = (p->reserved[1] & FLACMI_FLAG_LPC_SIGN) != 0;
         if (int rc = get_window(ctx, k.n, (double**)&a.window, &a.fuse_lo, &a.fuse_hi)) return rc;
+        a.bound = ebound ? (uint32_t*)ctx->bound.p + 2 * k.unit0 : nullptr;
         if (b->sample_bits > 26) a.fuse_lo = a.fuse_hi = 0; /* products must stay below 2^52 */
         a.log2thr = ctx->d_log2thr;
         a.rec = (int32_t*)ctx->rec.p + k.unit0 * rec_words;
@@ -627,8 +667,13 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         a.stream = use_stream();
         /* every bound the kernels hold proves "LPC loses", the rare case once the predictor has
          * its sign: FLACMI_FLAG_LPC_SIGN computes every candidate's exact sum */
-        a.prune = p->mode == FLACMI_MODE_REFERENCE && !o->lpc_sums &&
-                  !(p->reserved[1] & (FLACMI_FLAG_ALL_CANDIDATES | FLACMI_FLAG_LPC_SIGN)) && prune_allowed();
+        a.prune = prune_call;
+        if (ebound) {
+            double* w = nullptr;
+            if (get_window(ctx, k.n, &w, nullptr, nullptr, &a.chunk_weight)) return hipErrorOutOfMemory;
+            a.bound = (const uint32_t*)ctx->bound.p + 2 * k.unit0;
+            a.energy = energy;
+        }
         a.sign_bound = !(p->reserved[1] & FLACMI_FLAG_TIERS_ONLY) && sign_bound_allowed();
         const bool wide = needs_wide(k.n, b->sample_bits, L, p->qlp_precision, p->mode);
         int path = (wide || o->residual_bytes == 8) ? 2 : (b->sample_bytes == 2 && p->qlp_precision <= 16) ? 0 : 1;

@@ -32,7 +32,13 @@ struct LpcArgs {
     double* acf;             /* optional [count][33] */
     int32_t fuse_lo, fuse_hi; /* window[i] == 1.0 exactly for i in [fuse_lo, fuse_hi) and
                                  |x| < 2^26 (0, 0: no fused blocks), see k_lpc */
+    uint32_t* bound;         /* optional [count][2]: the energy bound's words for k_resid_stream (lpc_finish);
+                                the window then holds kBoundLags more values behind its pad: kappa_1 .. */
 };
+/* the energy bound: the word pair of a unit it must not decide, and the lags
+ * k = 1 .. kBoundLags of kappa_k = max_i |w_i - w_{i-k}| stored at window[n + kWindowPad ..] */
+constexpr uint32_t kBoundUnusable = 0xffffffffu;
+constexpr int kBoundLags = 13;
 
 struct ResidArgs {
     const void* samples;
@@ -77,6 +83,10 @@ struct ResidArgs {
     int32_t persist;                 /* k_resid kVarMf8: the grid loops over the batch and copies the next
                                         unit's samples into LDS (LDS-DMA) during this unit's Rice phase */
     int32_t sign_bound;              /* int8-MFMA pruning: try the sign-correlation bound before the tiers */
+    const uint32_t* bound;           /* k_resid_stream's batch kernel: k_lpc's energy-bound words [count][2] and */
+    const uint16_t* chunk_weight;    /* [n / 8] floor(256 min window weight) per 8-sample chunk (NULL: no pre-test) */
+    int32_t energy;                  /* knob FLACMI_ENERGY_BOUND: 1 = pre-test, then the tiers; 2 = pre-test, then
+                                        the exact pass; 0 = the tiers alone */
 };
 /* internal unit status between the fast and the generic k_resid (never returned) */
 #define FLACMI_STATUS_RETRY 0x7e
@@ -233,7 +243,7 @@ ResidLaunch resid_launch_config(int n, int rmax_eff, int residual_bytes);
 constexpr int kMaxFinestParts = 4096;
 
 /* flacmi_set_knob's knobs: the environment's value (read once) or the last value set */
-enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobCount };
+enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobEnergyBound, kKnobCount };
 int knob(Knob k);
 
 hipError_t launch_lpc(const LpcArgs& a, hipStream_t s);

@@ -26,9 +26,27 @@ __device__ __forceinline__ void write_quant(int32_t* rec, int L, int p, const in
 
 /* Levinson-Durbin at max order with a snapshot per order (encoder.py:453-479), each
  * snapshot quantised (encoder.py:482-534), into the unit's LPC record */
-template <int LMAX>
-__device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const LpcArgs& a, int32_t* __restrict__ rec) {
+/* EB (the builds that feed k_resid_stream: int16 samples, LMAX <= 12) with a.bound set: two
+ * words per unit from which the stream kernel proves that LPC loses without touching a
+ * sample ("energy bound").  With the record's coefficients (the reference's
+ * Levinson returns the negated predictor) r_i = x_i - floor(P_i), and e_i = x_i + P_i is
+ * the residual of the properly signed predictor, whose energy on the windowed signal is
+ * the quadratic form alpha' R alpha of this lane's autocorrelation, alpha = (1, c / 2^s):
+ *   E_p  = sum_l g_l acf_l / 2^2s,  g_l = sum_j a_j a_{j+l} (twice for l > 0), a = (2^s, c),
+ *          plus (sum|a| / 2^s)^2 acf_0 2^-39 for the f64 sums' rounding,
+ *   U2_p = sum_j |c_j| / 2^s kappa_{j+1}, kappa_k = max_i |w_i - w_{i-k}| (behind the
+ *          window's zero pad).
+ * Words: ceil(sqrt(n max_p E_p)) + 1 and ceil(256 max_p U2_p) + 1, or kBoundUnusable twice
+ * for a unit with a status, a negative-shift order or a value that is not finite. */
+template <int LMAX, bool EB = false>
+__device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const LpcArgs& a, int32_t* __restrict__ rec,
+                                           uint32_t* __restrict__ bound = nullptr) {
     const int L = a.L, q = a.q;
+    const bool eb = EB && bound != nullptr; /* wave-uniform */
+    const __attribute__((address_space(4))) double* kap =
+        (const __attribute__((address_space(4))) double*)a.window + a.n + kWindowPad - 1; /* kap[k], k = 1 .. 13 */
+    double emax = 0.0, u2max = 0.0;
+    bool ebad = false;
     const pym::PowTables PT{c_log_hdr, c_log_tab, c_exp_hdr, c_exp_tab};
     double c[LMAX + 1];
     c[0] = 1.0;
@@ -97,6 +115,7 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
                          * sites depend on |c| alone): +-2^|shift|, pow2_exact with the sign bit */
                         const double scale = pym::as_double(((uint64_t)(1023 + (neg ? -shift : shift)) << 52) | sign);
                         double e = 0.0;
+                        double aq[EB ? LMAX + 1 : 1]; /* EB: (2^shift, the quantised coefficients), exact */
 #pragma unroll
                         for (int j = 1; j <= LMAX; ++j) {
                             if (j <= p && qst == ST_OK) {
@@ -112,6 +131,7 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
                                     const double qq = r < qmin ? qmin : (r > qmax ? qmax : r);
                                     e = e - qq;
                                     cq[j - 1] = (int32_t)qq;
+                                    if constexpr (EB) aq[j] = qq;
                                 }
                             }
                         }
@@ -124,6 +144,29 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
                                     if (j < p) cq[j] = 0;
                             }
                             rec[2 + p - 1] = shift;
+                            if constexpr (EB) {
+                                if (eb && !neg) {
+                                    /* integers below 2^36: every product and partial sum is exact in f64 */
+                                    aq[0] = pym::as_double((uint64_t)(1023 + shift) << 52);
+                                    const double inv = pym::as_double((uint64_t)(1023 - shift) << 52);
+                                    double en = 0.0, sa = 0.0, u2 = 0.0;
+#pragma unroll
+                                    for (int l = 0; l <= p; ++l) {
+                                        double g = 0.0;
+#pragma unroll
+                                        for (int j = 0; j + l <= p; ++j) g = __builtin_fma(aq[j], aq[j + l], g);
+                                        en = __builtin_fma(l > 0 ? g + g : g, acc[l], en);
+                                        sa = sa + __builtin_fabs(aq[l]);
+                                        if (l > 0) u2 = __builtin_fma(__builtin_fabs(aq[l]), kap[l], u2);
+                                    }
+                                    sa = sa * inv;
+                                    en = en * inv * inv + sa * sa * acc[0] * 0x1p-39;
+                                    u2 = u2 * inv;
+                                    ebad |= !(en >= 0.0 && en < 0x1p80 && u2 < 0x1p40);
+                                    emax = en > emax ? en : emax;
+                                    u2max = u2 > u2max ? u2 : u2max;
+                                }
+                            }
                         }
                     }
                 }
@@ -138,6 +181,14 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
     }
     rec[0] = st | (site << 16);
     rec[1] = (int32_t)negmask;
+    if constexpr (EB) {
+        if (eb) {
+            const double u1 = __builtin_ceil(__builtin_sqrt((double)a.n * emax) * (1.0 + 0x1p-40)) + 1.0;
+            const double u2 = __builtin_ceil(256.0 * u2max * (1.0 + 0x1p-40)) + 1.0;
+            const bool ok = st == ST_OK && negmask == 0 && !ebad && u1 < 4294967295.0 && u2 < 4294967295.0;
+            *reinterpret_cast<uint2*>(bound) = ok ? uint2{(uint32_t)u1, (uint32_t)u2} : uint2{kBoundUnusable, kBoundUnusable};
+        }
+    }
 }
 
 /* ACF_IN: the autocorrelation is read from a.acf ([count][33]) instead of computed from
@@ -347,7 +398,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lpc_waves(L
     }
     } /* !ACF_IN */
 
-    lpc_finish<LMAX>(acc, a, rec);
+    constexpr bool EB = !ACF_IN && LMAX <= 12 && sizeof(SampleT) == 2;
+    lpc_finish<LMAX, EB>(acc, a, rec, EB && a.bound ? a.bound + 2 * gid : nullptr);
 }
 
 
@@ -490,7 +542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LMAX <= 12 
 #pragma unroll
         for (int l = 0; l < 33; ++l) o[l] = (l <= LMAX && l <= L) ? acc[l < LMAX ? l : LMAX] : 0.0;
     }
-    lpc_finish<LMAX>(acc, a, rec);
+    lpc_finish<LMAX, (LMAX <= 12)>(acc, a, rec, a.bound ? a.bound + 2 * gid : nullptr);
 }
 
 
@@ -519,6 +571,7 @@ static hipError_t launch_lpc_T(const LpcArgs& a, hipStream_t s) {
             r.unit0 += full;
             r.count = a.count - full;
             r.rec += full * a.rec_words;
+            if (r.bound) r.bound += 2 * full;
             if (r.acf) r.acf += full * 33;
             hipLaunchKernelGGL((k_lpc<LMAX, int16_t>), dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r);
             return hipGetLastError();

@@ -80,7 +80,7 @@ struct SLds {
  *   rec  the LPC orders' f16 tap table (aliases pk, tap_table)  staging .. MFMA operands
  *   red  u64 [nw][group][order] MFMA partial sums               MFMA phase .. choice
  *   red2 u64 [nw + 1][order] data bits (aliases red)            Rice (after B3)
- *   red0 u32 [nw] sum|x|                                         staging .. choice
+ *   red0 u32 [2 nw] sum|x|, then the energy bound's weighted sums   staging .. choice
  *        (word 0 then: the Rice table's error flag                 B3 .. B3b)
  *   pks  u32 [P] finest partition sums                          staging (zeroed) .. Rice */
 __host__ __device__ inline SLds stream_lds(int n, int nw, int tap_words, int P, int RS) {
@@ -91,7 +91,7 @@ __host__ __device__ inline SLds stream_lds(int n, int nw, int tap_words, int P, 
     l.xs = o;   o = up(o + 2 * (kSHP + n));
     l.pk = l.rec = o; o = up(o + mx(2 * P * RS, 4 * mx(tap_words, 1)));
     l.red = l.red2 = o; o = up(o + mx(8 * nw * 16, 8 * (nw + 1) * kRiceOrders));
-    l.red0 = o; o = up(o + 4 * nw);
+    l.red0 = o; o = up(o + 8 * nw);
     l.pks = o;  o = up(o + 4 * P);
     l.total = o;
     return l;
@@ -324,8 +324,14 @@ __device__ __forceinline__ void store_meta(flacmi_unit_meta* m, int lane, const 
  * whatever the shift; every LPC value is then exact, |r| = |x - floor(pred / 2^shift)| by a
  * shift, a subtract and one v_sad_u32 (no pruning tiers: the units a large shift lists are
  * mostly near-ties no bound decides).  A unit outside even that bound goes to the second list
- * (k_resid's list variant). */
-template <int NG, bool R05, int NFIX, bool LIST, typename Args>
+ * (k_resid's list variant).
+ * EB (batch kernel, NG > 0, a.prune): the energy bound's pre-test.  The fixed group
+ * runs over every block first; then 2 W - 256 (U1 + n) - U2 F0 > 256 fmin, from k_lpc's two words
+ * (U1, U2), the exact order-0 sum F0 and W = sum_chunks weight * sum_chunk |x| gathered in
+ * staging, proves that every LPC order loses, and no LPC group runs at all.  An undecided
+ * unit runs tier 0 as a loop of its own, then the tiers as before (a.energy == 2: the exact
+ * pass at once). */
+template <int NG, bool R05, int NFIX, bool LIST, bool EB, typename Args>
 __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, unsigned char* smem) {
     /* NFIX: the block length (and L = 4 NG, the workgroup size) as compile-time constants, the
      * BASELINE configs' 4608-sample units: loop bounds, chunk guards and partition indices fold */
@@ -378,6 +384,11 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
 #endif
         }
         fixb = reinterpret_cast<const uint4*>(kFixB.w)[lane];
+        uint32_t cwv[EB ? kSCPT : 1]; /* the chunks' weights (1/256) */
+        if constexpr (EB) {
+#pragma unroll
+            for (int j = 0; j < kSCPT; ++j) cwv[j] = a.chunk_weight[min(tid + j * NT, nch - 1)];
+        }
         /* tap table words tid + j NT: word w of row p holds (T_p[16 - 2w], T_p[15 - 2w]); the
          * record values it needs are loaded here, with the samples (clamped, unconditional) */
         constexpr int kTW = tap_table_words(NG), kTJ = NG > 0 ? (kTW + 63) / 64 : 0;
@@ -401,7 +412,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
 #else
         const uint32_t k8000 = opaque(0x8000u);
 #endif
-        uint32_t sumx = 0;
+        uint32_t sumx = 0, wsum = 0;
 #pragma unroll
         for (int j = 0; j < kSCPT; ++j) {
             const int v = tid + j * NT;
@@ -409,16 +420,27 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                 const uint4 y{q[j].x ^ 0x80008000u, q[j].y ^ 0x80008000u, q[j].z ^ 0x80008000u, q[j].w ^ 0x80008000u};
                 *reinterpret_cast<uint4*>(xs + 8 * v) = y;
                 const uint32_t yd[4] = {y.x, y.y, y.z, y.w};
+                if constexpr (EB) {
+                    /* the chunk's sum|x| on its own (< 2^18), then once into sumx and, times the
+                     * chunk's weight (<= 256), into wsum (per lane below 2^29) */
+                    static_assert(FLACMI_SAD16, "the energy bound's staging uses v_sad_u16");
+                    uint32_t part = 0;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
+                    for (int e = 0; e < 4; ++e) part = __builtin_amdgcn_sad_u16(yd[e], k8000, part);
+                    sumx += part;
+                    wsum += __umul24(part, cwv[j]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
 #if FLACMI_SAD16
-                    /* one v_sad_u16 per dword: |lo - 0x8000| + |hi - 0x8000| + sumx (per lane at
-                     * most 8 kSCPT samples of 2^15: far below 2^32) */
-                    sumx = __builtin_amdgcn_sad_u16(yd[e], k8000, sumx);
+                        /* one v_sad_u16 per dword: |lo - 0x8000| + |hi - 0x8000| + sumx (per lane at
+                         * most 8 kSCPT samples of 2^15: far below 2^32) */
+                        sumx = __builtin_amdgcn_sad_u16(yd[e], k8000, sumx);
 #else
-                    sumx = sad32(yd[e] & 0xffffu, k8000, sumx);
-                    sumx = sad32(yd[e] >> 16, k8000, sumx);
+                        sumx = sad32(yd[e] & 0xffffu, k8000, sumx);
+                        sumx = sad32(yd[e] >> 16, k8000, sumx);
 #endif
+                    }
                 }
             }
         }
@@ -439,6 +461,10 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         }
         const uint32_t sx = wave_sum_u32(sumx);
         if (lane == 0) red0[wid] = sx;
+        if constexpr (EB) { /* in eighths, rounded down per lane: the wave's sum stays below 2^32 */
+            const uint32_t sw = wave_sum_u32(wsum >> 3);
+            if (lane == 0) red0[nw + wid] = sw;
+        }
     }
     STAMP(1);
     __syncthreads(); /* B1 */
@@ -473,14 +499,14 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
      * block (a workgroup-uniform branch: every wave decides from the same LDS words). */
     const bool prune = NG > 0 && a.prune && !LIST;
     unsigned long long* red64 = reinterpret_cast<unsigned long long*>(smem + lay.red); /* [nw][4 groups][4 orders] */
-    auto lane_total = [&]() __attribute__((always_inline)) -> uint64_t {
+    auto lane_total = [&](bool with_lpc = true) __attribute__((always_inline)) -> uint64_t {
         /* lanes 1..4: fixed orders 1..4, lane 0: order 0 (sum|x|), lanes 16..15+4NG: LPC orders */
         uint64_t t = 0;
         int g = -1, o4l = 0;
         if (lane >= 1 && lane <= 4) {
             g = 0;
             o4l = lane - 1;
-        } else if (NG > 0 && lane >= 16 && lane < 16 + 4 * NG) {
+        } else if (NG > 0 && with_lpc && lane >= 16 && lane < 16 + 4 * NG) {
             g = 1 + ((lane - 16) >> 2);
             o4l = (lane - 16) & 3;
         }
@@ -638,11 +664,11 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
          * 4 kb rows; the lanes with rho == 0 and kb == 0 store.  BD: the LPC groups hold the
          * bound sum |T|, stored as floor(acc / 2^shift) per lane (a lower bound of the sum of
          * |T| / 2^shift; acc itself keeps accumulating over later tiers) */
-        auto reduce_store = [&](auto g0c, auto bdc) __attribute__((always_inline)) {
-            constexpr int G0 = decltype(g0c)::value;
+        auto reduce_store = [&](auto g0c, auto bdc, auto g1c) __attribute__((always_inline)) {
+            constexpr int G0 = decltype(g0c)::value, G1 = decltype(g1c)::value;
             constexpr bool BD = decltype(bdc)::value != 0;
 #pragma unroll
-            for (int g = G0; g <= NG; ++g) {
+            for (int g = G0; g <= G1; ++g) {
                 uint32_t v = (BD && g > 0) ? acc[g] >> shg[g] : acc[g];
                 v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);
                 v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);
@@ -657,7 +683,12 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         using ING = std::integral_constant<int, NG>;
         /* this wave's blocks wid + k nw, k = 0 .. kw - 1 (wave 0 takes block 0 masked, last) */
         const int kw = (nblk - wid + nw - 1) / nw;
-        if (prune) {
+        if (EB && prune) {
+            /* the fixed group alone over every block: the pre-test below needs the fixed sums */
+            for (int k = wid == 0 ? 1 : 0; k < kw; ++k) blockA(I0{}, I0{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
+            if (wid == 0) block(I0{}, I0{}, I0{}, ld0(), true, 0);
+            reduce_store(I0{}, I0{}, I0{});
+        } else if (prune) {
             /* tier 0: the wave's blocks k % 4 == 0 run the LPC groups (bound) beside the fixed
              * group; tiers 1..3 (only while the bound has not decided) add k % 4 == 2, 1, 3 */
             const bool no_lpc = a.stop_after == 12; /* ablation (timing only): no LPC bound at all */
@@ -667,16 +698,16 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                 if ((k & 3) == 0 && !no_lpc) blockA(I1{}, ING{}, I0{}, A, false, xnone);
             }
             if (wid == 0) block(I0{}, ING{}, I0{}, ld0(), true, 0);
-            reduce_store(I0{}, I1{});
+            reduce_store(I0{}, I1{}, ING{});
         } else {
             for (int blk = wid == 0 ? nw : wid; blk < nblk; blk += nw) block(I0{}, ING{}, I1{}, ld(blk), false, blk);
             if (wid == 0) block(I0{}, ING{}, I1{}, ld0(), true, 0);
-            reduce_store(I0{}, I0{});
+            reduce_store(I0{}, I0{}, ING{});
             if constexpr (LIST) mv.tiers = 1 | (1 << 8); /* one exact pass (the listed units' marker) */
         }
         __syncthreads(); /* B2 */
         STAMP(3);
-        tj = lane_total();
+        tj = lane_total(!(EB && prune));
         if constexpr (NG > 0) {
             if (prune) {
                 /* best fixed sum (exact) against every LPC order's lower bound */
@@ -687,8 +718,36 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                 fk = dpp_min_u64<0x140>(fk);
                 const uint64_t fmin = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fk >> 32), 0) << 28) |
                                       ((uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)fk, 0) >> 4);
+                bool tiers = true;
+                if constexpr (EB) {
+                    /* the pre-test, in integers (u64, every wave alike): W >= 8 Wr, so
+                     * 16 Wr > 256 (U1 + n + fmin) + U2 F0 proves the bound above fmin for every
+                     * order.  Unusable words (kBoundUnusable) never pass: 16 Wr < 2^40. */
+                    uint64_t wr = 0;
 #pragma unroll 1
-                for (int t = 1;; ++t) {
+                    for (int w2 = 0; w2 < nw; ++w2) wr += red0[nw + w2];
+                    const uint2 bw = *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
+                    const uint64_t f0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tj >> 32), 0) << 32) |
+                                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tj, 0);
+                    const uint64_t rhs = 256ull * ((uint64_t)bw.x + (uint64_t)n + fmin) + (uint64_t)bw.y * f0;
+                    if (bw.x != kBoundUnusable && 16ull * wr > rhs) {
+                        pruned = true;
+                        tiers = false;
+                        mv.tiers = 1 | (4 << 8);
+                    } else if (a.energy == 2) {
+                        tiers = false; /* (tests, hit-rate counts) straight to the exact pass */
+                    } else {
+                        /* tier 0 after all: the LPC groups (bound) over the wave's blocks k % 4 == 0,
+                         * the masked block 0 among them; their red64 slots are not the fixed group's */
+                        for (int k = wid == 0 ? 4 : 0; k < kw; k += 4) blockA(I1{}, ING{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
+                        if (wid == 0) block(I1{}, ING{}, I0{}, ld0(), true, 0);
+                        reduce_store(I1{}, I1{}, ING{});
+                        __syncthreads();
+                        tj = lane_total();
+                    }
+                }
+#pragma unroll 1
+                for (int t = 1; tiers; ++t) {
                     const uint64_t lb = tj > (uint64_t)n ? tj - (uint64_t)n : 0ull;
                     const uint64_t open = __ballot(lane >= 16 && lane < 16 + L && lb <= fmin);
                     pruned = open == 0 || a.stop_after >= 11; /* 11, 12: ablation, tier 0 only */
@@ -709,7 +768,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                             }
                         }
                     }
-                    reduce_store(I1{}, I1{});
+                    reduce_store(I1{}, I1{}, ING{});
                     __syncthreads();
                     tj = lane_total();
                 }
@@ -720,7 +779,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                     for (int g = 1; g <= NG; ++g) acc[g] = 0;
                     for (int blk = wid == 0 ? nw : wid; blk < nblk; blk += nw) block(I1{}, ING{}, I1{}, ld(blk), false, blk);
                     if (wid == 0) block(I1{}, ING{}, I1{}, ld0(), true, 0);
-                    reduce_store(I1{}, I0{});
+                    reduce_store(I1{}, I0{}, ING{});
                     __syncthreads();
                     tj = lane_total();
                 }
@@ -1183,10 +1242,10 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
 typedef const __attribute__((address_space(4))) ResidArgs* StreamKernarg;
 
 /* one workgroup per unit of the batch */
-template <int NG, bool R05, int NFIX = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R05 ? 8 : 7, 8))) void k_resid_stream(ResidArgs a) {
+template <int NG, bool R05, int NFIX = 0, bool EB = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((R05 || EB) ? 8 : 7, 8))) void k_resid_stream(ResidArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    stream_unit<NG, R05, NFIX, false>(a, blockIdx.x, smem);
+    stream_unit<NG, R05, NFIX, false, EB>(a, blockIdx.x, smem);
 }
 
 /* the units k_resid_stream listed (a.retry_list), pred-only taps: a fixed grid whose
@@ -1211,7 +1270,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
         asm volatile("" : "+s"(pa));
         const int r = __builtin_popcountll(__ballot(incl <= k)); /* incl[r - 1] <= k < incl[r] */
         const uint32_t base = r > 0 ? (uint32_t)__builtin_amdgcn_readlane((int)incl, r - 1) : 0u;
-        stream_unit<NG, R05, NFIX, true>(*pa, pa->retry_list[r * pa->retry_sub_cap + (k - base)], smem);
+        stream_unit<NG, R05, NFIX, true, false>(*pa, pa->retry_list[r * pa->retry_sub_cap + (k - base)], smem);
         __syncthreads(); /* every wave is done with this unit's LDS */
     }
 }
@@ -1253,6 +1312,8 @@ static hipError_t launch_stream_K(const ResidArgs& a, bool list, hipStream_t s) 
         if (a.n % (1 << o) == 0) rmax_eff = o;
     const size_t lds = stream_lds(a.n, nt / 64, tap_table_words(NG), 1 << rmax_eff, kRiceOrders).total;
     auto kern = list ? k_resid_stream_list<NG, R05, NFIX> : k_resid_stream<NG, R05, NFIX>;
+    if constexpr (NG > 0) /* the energy bound's build of the batch kernel (knob FLACMI_ENERGY_BOUND) */
+        if (!list && a.prune && a.energy != 0 && a.bound && a.chunk_weight) kern = k_resid_stream<NG, R05, NFIX, true>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(list ? stream_list_grid(a.count) : (unsigned)a.count), dim3(nt), lds, s, a);

@@ -701,7 +701,9 @@ int flacmi_timing_reset(flacmi_ctx* ctx);
  * for samples of <= 16 bits, else 4 KB), 6 / 8 = the ring writer built for 256 / 128
  * threads, 7 = as 2 with the one-window writer on its 16 KB window only), "FLACMI_DECODE_LPC"
  * (0 = no second fast-decoder pass for LPC subframes: those frames go to the general decoder
- * kernel; default 1).
+ * kernel; default 1), "FLACMI_ENERGY_BOUND" (the stream kernel's pruning calls: 1 = prove LPC's
+ * loss from the autocorrelation first, then the partial-sum tiers (default); 0 = the tiers
+ * alone; 2 = that proof, then the exact sums; same results but for meta.lpc_tiers).
  * FLACMI_E_INVALID for any other name.  No device needed. */
 int flacmi_set_knob(const char* name, int32_t value);
 int flacmi_get_knob(const char* name, int32_t* value);
