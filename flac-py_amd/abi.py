@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 5  # include/flacmi.h FLACMI_ABI_VERSION
+ABI_VERSION = 6  # include/flacmi.h FLACMI_ABI_VERSION
 MAX_LPC_ORDER = 32
 MAX_BLOCK = 65535
 MAX_RICE_ORDER = 15
@@ -274,6 +274,83 @@ class StreamResult(C.Structure):
     ]
 
 
+class FrameInfo(C.Structure):
+    _fields_ = [
+        ("offset", C.c_int64),
+        ("end", C.c_int64),
+        ("coded_number", C.c_int64),
+        ("status", C.c_int32),
+        ("block_size", C.c_int32),
+        ("blocking_strategy", C.c_int32),
+        ("sample_rate", C.c_int32),
+        ("sample_size", C.c_int32),
+        ("channel_code", C.c_int32),
+        ("n_subframes", C.c_int32),
+        ("header_bytes", C.c_int32),
+        ("crc8_stored", C.c_int32),
+        ("crc8_computed", C.c_int32),
+        ("crc16_stored", C.c_int32),
+        ("crc16_computed", C.c_int32),
+        ("padding_bits", C.c_int32),
+        ("reserved0", C.c_int32),
+    ]
+
+
+class SubframeInfo(C.Structure):
+    _fields_ = [
+        ("bit_offset", C.c_int64),
+        ("bits", C.c_int64),
+        ("type", C.c_int32),
+        ("order", C.c_int32),
+        ("wasted_bits", C.c_int32),
+        ("sample_bits", C.c_int32),
+        ("precision", C.c_int32),
+        ("shift", C.c_int32),
+        ("coefficients", C.c_int16 * MAX_LPC_ORDER),
+        ("coding_method", C.c_int32),
+        ("partition_order", C.c_int32),
+        ("escaped_partitions", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("residual_bits", C.c_int64),
+        ("abs_sum", C.c_int64),
+        ("constant_value", C.c_int64),
+        ("partitions_stored", C.c_int32),
+        ("reserved1", C.c_int32),
+    ]
+
+
+def _np_dtype(struct) -> np.dtype:
+    """The numpy record dtype of a ctypes struct of int16/32/64 fields and arrays of them."""
+    kinds = {C.c_int16: "<i2", C.c_int32: "<i4", C.c_int64: "<i8"}
+    fields = []
+    for name, t in struct._fields_:
+        fields.append((name, kinds[t._type_], (t._length_,)) if hasattr(t, "_length_") else (name, kinds[t]))
+    return np.dtype(fields)
+
+
+# numpy views of flacmi_frame_info / flacmi_subframe_info
+FRAME_INFO_DTYPE = _np_dtype(FrameInfo)
+SUBFRAME_INFO_DTYPE = _np_dtype(SubframeInfo)
+assert FRAME_INFO_DTYPE.itemsize == C.sizeof(FrameInfo) == 80
+assert SUBFRAME_INFO_DTYPE.itemsize == C.sizeof(SubframeInfo) == 152
+SUB_TYPE_CONSTANT, SUB_TYPE_VERBATIM, SUB_TYPE_FIXED, SUB_TYPE_LPC = 0, 1, 2, 3  # flacmi_subframe_type
+SUB_TYPE_NAMES = ("CONSTANT", "VERBATIM", "FIXED", "LPC")
+PART_ESCAPE = 0x80  # part_params byte of an escaped partition: 0x80 | width
+
+
+class InfoResult(C.Structure):
+    _fields_ = [
+        ("frames", C.c_int64),
+        ("consumed", C.c_int64),
+        ("status", C.c_int32),
+        ("site", C.c_int32),
+        ("candidates", C.c_int64),
+        ("probes", C.c_int64),
+        ("full", C.c_int64),
+        ("reserved0", C.c_int64),
+    ]
+
+
 COMM_ID_BYTES = 128  # FLACMI_COMM_ID_BYTES
 
 # Every symbol include/flacmi.h declares, with its ctypes signature.
@@ -320,6 +397,12 @@ SIGNATURES = {
     "flacmi_decode_stream_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DecodeParams),
                                             C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                             C.POINTER(StreamResult)]),
+    "flacmi_frame_info_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.POINTER(DecodeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_void_p]),
+    "flacmi_info_stream_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DecodeParams),
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                          C.POINTER(InfoResult)]),
     "flacmi_stream_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                       C.c_int64, C.c_void_p, C.c_void_p]),
     "flacmi_comm_available": (C.c_int, []),

@@ -459,6 +459,55 @@ class Analyzer:
                                                  C.byref(res)), "flacmi_decode_stream_host")
         return res
 
+    # ------------------------------------------------------------------------------
+    # stream analysis (include/flacmi.h flacmi_frame_info_device / flacmi_info_stream_host)
+    # ------------------------------------------------------------------------------
+    def frame_info(self, data, offsets, channels: int, sample_size: int, part_stride: int = 64,
+                   sentinel: int = 0xEE):
+        """Host bytes and frame starts in -> (FRAME_INFO_DTYPE [n], SUBFRAME_INFO_DTYPE [n][channels],
+        part_params uint8 [n][channels][part_stride]) from k_frame_info.  The three arrays are
+        filled with `sentinel` bytes first, so what the kernel did not write shows."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        nb, n = int(len(data)), len(offsets)
+        buf = torch.zeros(((nb + 3) // 4) * 4 + 16, dtype=torch.uint8, device=dev)
+        if nb:
+            buf[:nb] = torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).to(dev)
+        off = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
+
+        def filled(nbytes):
+            return torch.full((max(nbytes, 8),), sentinel, dtype=torch.uint8, device=dev)
+        fi = filled(n * abi.FRAME_INFO_DTYPE.itemsize)
+        si = filled(n * channels * abi.SUBFRAME_INFO_DTYPE.itemsize)
+        pp = filled(n * channels * part_stride)
+        dp = abi.DecodeParams()
+        dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, 0
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self.lib.flacmi_frame_info_device(self.ctx, buf.data_ptr(), nb, off.data_ptr(), n, C.byref(dp),
+                                                fi.data_ptr(), si.data_ptr(), pp.data_ptr() if part_stride else None,
+                                                part_stride, stream), "flacmi_frame_info_device")
+        torch.cuda.synchronize(dev)
+        return (fi.cpu().numpy()[:n * abi.FRAME_INFO_DTYPE.itemsize].view(abi.FRAME_INFO_DTYPE),
+                si.cpu().numpy()[:n * channels * abi.SUBFRAME_INFO_DTYPE.itemsize].view(abi.SUBFRAME_INFO_DTYPE)
+                .reshape(n, channels),
+                pp.cpu().numpy()[:n * channels * part_stride].reshape(n, channels, part_stride))
+
+    def info_stream(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
+                    final_chunk: bool, frames: np.ndarray, subframes: np.ndarray, parts: np.ndarray) -> abi.InfoResult:
+        """flacmi_info_stream_host: one chunk of host stream bytes -> the records of its frames
+        in frames [capacity] (FRAME_INFO_DTYPE), subframes [capacity][channels]
+        (SUBFRAME_INFO_DTYPE) and parts [capacity][channels][part_stride] (uint8)."""
+        dp = abi.DecodeParams()
+        dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, 0
+        res = abi.InfoResult()
+        part_stride = parts.shape[2]
+        assert subframes.shape == (len(frames), channels) and parts.shape[:2] == (len(frames), channels)
+        check(self.lib.flacmi_info_stream_host(self.ctx, data_ptr, nbytes, first_byte, C.byref(dp), int(final_chunk),
+                                               frames.ctypes.data, subframes.ctypes.data,
+                                               parts.ctypes.data if part_stride else None, part_stride, len(frames),
+                                               C.byref(res)), "flacmi_info_stream_host")
+        return res
+
     def timing(self) -> dict:
         """Average k_lpc / k_resid / whole-call milliseconds over the analyze calls since
         the last timing_reset() (HIP events recorded on each call's stream)."""

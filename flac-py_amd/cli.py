@@ -1,5 +1,6 @@
 """Command line with flac/__main__.py's `encode` and `decode` actions (their arguments,
-defaults and output bytes), on the device path.  encode: streamed PCM ingest (ingest.iter_wav_pcm, the
+defaults and output bytes), on the device path, and `analyze`, the per-frame report flac-py's
+README wishes for ("a tool providing information about a FLAC file, as `flac -a` does").  encode: streamed PCM ingest (ingest.iter_wav_pcm, the
 reference reader's byte grouping unless --correct-reader), device analysis and device
 frame writer through the streaming pipeline (encoder.encode_wav); --devices spreads the
 batches over several GPUs.
@@ -15,6 +16,17 @@ decode (__main__.py:27-55 cmd_decode): the stream's frames are found, decoded, i
 packed on the device (decoder.decode_wav over flacmi_decode_stream_host) and written through
 the wave module as the reference does; --check-crc also verifies CRC-8 / CRC-16, which the
 reference reads unchecked.
+
+    python -m flac_amd analyze infile.flac [--partitions] [--json] [--summary-only] [--device N]
+
+analyze (flac_amd.info over flacmi_info_stream_host): tab-separated key=value lines in stream
+order, one per metadata block, one per frame (frame=, offset=, bytes=, blocksize=, sample_rate=,
+sample_size=, channel_assignment=, number=, crc8=ok|BAD, crc16=ok|BAD) and one indented line per
+subframe (subframe=, type=, order=, wasted_bits=, bits=, and where they apply precision=, shift=,
+coefficients=, residual_type=, partition_order=, abs_sum=; --partitions adds the Rice parameters,
+an escaped partition as e<width>), then the summary block.  --json writes one JSON object per
+line instead.  Where the reference would raise inside a frame, a `stopped` line names the frame
+and the exception after the summary, and the exit status is 1.
 """
 import argparse
 import sys
@@ -61,7 +73,55 @@ def make_argument_parser():
     dec.add_argument("--device", type=int, default=0)
     dec.add_argument("--check-crc", action="store_true",
                      help="verify the frames' CRC-8 and CRC-16 (the reference reads them unchecked)")
+    ana = action.add_parser("analyze", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ana.add_argument("infile", type=Path, metavar="infile.flac")
+    ana.add_argument("--partitions", action="store_true", help="list every subframe's Rice parameters")
+    ana.add_argument("--json", action="store_true", help="one JSON object per line instead of key=value text")
+    ana.add_argument("--summary-only", action="store_true", help="no metadata, frame and subframe lines")
+    ana.add_argument("--device", type=int, default=0)
     return parser
+
+
+def cmd_analyze(args) -> int:
+    import json
+    from . import info
+    report = info.analyze(args.infile, device=args.device)
+    out = sys.stdout
+    if not args.summary_only:
+        if args.json:
+            si = report.streaminfo
+            out.write(json.dumps({"streaminfo": {k: (v.hex() if isinstance(v, bytes) else v) for k, v in vars(si).items()},
+                                  "first_frame_offset": report.first_frame_offset}) + "\n")
+            for k, (t, length, offset, last) in enumerate(report.metadata):
+                out.write(json.dumps({"metadata": k, "type": t.name.upper(), "length": length, "offset": offset,
+                                      "last": int(last)}) + "\n")
+        else:
+            out.write("".join(ln + "\n" for ln in info.format_metadata(report.metadata)))
+    frames = []
+    try:
+        for fr in report.frames:
+            frames.append(fr)
+            if args.summary_only:
+                continue
+            if args.json:
+                out.write(json.dumps({"frame": info.frame_json(fr)}) + "\n")
+            else:
+                out.write("".join(ln + "\n" for ln in info.format_frame(fr, report.streaminfo, args.partitions)))
+    except Exception as e:  # noqa: BLE001  -- reported after the summary of the frames before it
+        report.exception = e
+    summary = info.summarize(report, frames)
+    if args.json:
+        out.write(json.dumps({"summary": info.summary_json(summary)}) + "\n")
+    else:
+        out.write("".join(ln + "\n" for ln in info.format_summary(summary)))
+    if report.exception is not None:
+        e = report.exception
+        if args.json:
+            out.write(json.dumps({"stopped": {"frame": len(frames), "exception": type(e).__name__, "message": str(e)}}) + "\n")
+        else:
+            out.write(f"stopped\tframe={len(frames)}\texception={type(e).__name__}\tmessage={e}\n")
+        return 1
+    return 0
 
 
 def cmd_decode(args) -> None:
@@ -90,6 +150,8 @@ def main(argv=None) -> int:
         cmd_encode(args)
     if args.action == "decode":
         cmd_decode(args)
+    if args.action == "analyze":
+        return cmd_analyze(args)
     return 0
 
 

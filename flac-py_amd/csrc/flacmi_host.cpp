@@ -169,6 +169,7 @@ struct flacmi_ctx {
     DevBuf h_subkind;           /* flacmi_encode_host's sub_kind array (FLACMI_FRAME_FALLBACK) */
     DevBuf h_side, h_choice;    /* flacmi_encode_host's side rows and per-frame choice (FLACMI_STEREO_BEST) */
     DevBuf idx, sd_data, sd_table, sd_meta, sd_rows, sd_pcm; /* frame index workspace; flacmi_decode_stream_host's buffers */
+    DevBuf si_frames, si_subs, si_parts; /* flacmi_info_stream_host's candidate records */
     int64_t frames_bytes = 0;   /* bytes of the last flacmi_encode_host call */
     static constexpr int kRing = 64;
     static constexpr int kMaxChunks = 8;
@@ -214,7 +215,7 @@ struct KnobDef {
     int dflt;
 };
 constexpr KnobDef kKnobs[kKnobCount] = {{"FLACMI_OVERLAP", -1}, {"FLACMI_MF8_GRID", 0}, {"FLACMI_STREAM_GENERIC", 0}, {"FLACMI_DECODE_GENERIC", 0},
-                                        {"FLACMI_PACK_GENERIC", 0}, {"FLACMI_DECODE_LPC", 1}, {"FLACMI_ENERGY_BOUND", 1}};
+                                        {"FLACMI_PACK_GENERIC", 0}, {"FLACMI_DECODE_LPC", 1}, {"FLACMI_ENERGY_BOUND", 1}, {"FLACMI_INFO_GRID", 0}};
 std::atomic<int> g_knob[kKnobCount];
 std::once_flag g_knob_once;
 void knobs_init() {
@@ -315,7 +316,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     enc_free(ctx->enc);
     for (auto& kv : ctx->windows) (void)hipFree(kv.second);
     for (auto& kv : ctx->chunk_weights) (void)hipFree(kv.second);
-    for (DevBuf* b : {&ctx->bound, &ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
+    for (DevBuf* b : {&ctx->bound, &ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->si_frames, &ctx->si_subs, &ctx->si_parts, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
                       &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice})
         if (b->p) (void)hipFree(b->p);
@@ -1499,6 +1500,187 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
     res->frames = nc;
     res->samples = first;
     res->pcm_bytes = first * ch * B;
+    res->consumed = w.pos;
+    res->status = stop & 0xFFFF;
+    res->site = (stop >> 16) & 0xFFFF;
+    return 0;
+}
+
+/* ---- stream analysis ------------------------------------------------------------------- */
+int flacmi_frame_info_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                             const int64_t* frame_offsets, int64_t n_frames, const flacmi_decode_params* dp,
+                             flacmi_frame_info* frame_info, flacmi_subframe_info* subframe_info,
+                             uint8_t* part_params, int64_t part_stride, void* stream) {
+    if (!ctx || !dp) return fail(FLACMI_E_INVALID, "null argument");
+    if (n_frames < 0 || stream_bytes < 0) return fail(FLACMI_E_INVALID, "negative size");
+    if (part_stride < 0 || part_stride > 32768) return fail(FLACMI_E_INVALID, "part_stride must be 0..32768");
+    if (n_frames == 0) return 0;
+    if (!stream_data || !frame_offsets || !frame_info || !subframe_info) return fail(FLACMI_E_INVALID, "null buffer");
+    if (part_stride > 0 && !part_params) return fail(FLACMI_E_INVALID, "null part_params");
+    if (((uintptr_t)stream_data & 3) != 0) return fail(FLACMI_E_INVALID, "stream_data must be 4-byte aligned");
+    if ((((uintptr_t)frame_info | (uintptr_t)subframe_info | (uintptr_t)frame_offsets) & 7) != 0)
+        return fail(FLACMI_E_INVALID, "frame_offsets, frame_info and subframe_info must be 8-byte aligned");
+    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = set_device(ctx)) return rc;
+    InfoArgs a{};
+    a.words = reinterpret_cast<const uint32_t*>(stream_data);
+    a.stream_bytes = stream_bytes;
+    a.n_words = (stream_bytes + 3) / 4;
+    a.offsets = frame_offsets;
+    a.n_frames = n_frames;
+    a.channels = dp->channels;
+    a.sample_size = dp->sample_size;
+    a.frames = frame_info;
+    a.subs = subframe_info;
+    a.parts = part_stride > 0 ? part_params : nullptr;
+    a.part_stride = (int32_t)part_stride;
+    a.crc_slice = ctx->d_crc;
+    HIP_TRY(launch_frame_info(a, knob(kKnobInfoGrid), (hipStream_t)stream));
+    return 0;
+}
+
+int flacmi_info_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                            const flacmi_decode_params* dp, int32_t final_chunk, flacmi_frame_info* frame_info,
+                            flacmi_subframe_info* subframe_info, uint8_t* part_params, int64_t part_stride,
+                            int64_t frame_capacity, flacmi_info_result* res) {
+    if (!ctx || !dp || !res) return fail(FLACMI_E_INVALID, "null argument");
+    if (bytes < 0 || first_byte < 0 || first_byte > bytes || frame_capacity < 0) return fail(FLACMI_E_INVALID, "bad size");
+    if (bytes > 0 && !data) return fail(FLACMI_E_INVALID, "null buffer");
+    if (frame_capacity > 0 && (!frame_info || !subframe_info)) return fail(FLACMI_E_INVALID, "null record buffer");
+    if (part_stride < 0 || part_stride > 32768) return fail(FLACMI_E_INVALID, "part_stride must be 0..32768");
+    if (part_stride > 0 && frame_capacity > 0 && !part_params) return fail(FLACMI_E_INVALID, "null part_params");
+    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    memset(res, 0, sizeof(*res));
+    res->consumed = first_byte;
+    if (bytes == first_byte) return 0;
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t ch = (size_t)dp->channels, ps = (size_t)part_stride;
+
+    /* 1. the chunk, 2. the index (as flacmi_decode_stream_host) */
+    if (int rc = ensure_buf(ctx->sd_data, (size_t)bytes + 32)) return rc;
+    uint8_t* d_data = (uint8_t*)ctx->sd_data.p;
+    HIP_TRY(hipMemcpyAsync(d_data, data, (size_t)bytes, hipMemcpyHostToDevice, s));
+    int64_t cap = bytes / 512 + 1024, n = 0;
+    for (;;) {
+        if (int rc = ensure_buf(ctx->sd_table, sizeof(flacmi_frame_candidate) * (size_t)cap + 16)) return rc;
+        int64_t* d_count = (int64_t*)ctx->sd_table.p;
+        if (int rc = flacmi_index_frames_device(ctx, d_data, bytes, first_byte,
+                                                (flacmi_frame_candidate*)((char*)ctx->sd_table.p + 16), cap, d_count, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(&n, d_count, sizeof(n), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (n <= cap) break;
+        cap = n;
+    }
+    res->candidates = n;
+    std::vector<flacmi_frame_candidate> table((size_t)n);
+    if (n) HIP_TRY(hipMemcpy(table.data(), (char*)ctx->sd_table.p + 16, sizeof(flacmi_frame_candidate) * (size_t)n, hipMemcpyDeviceToHost));
+
+    /* 3. k_frame_info over every candidate (slot n: the probes'), 4. the records out */
+    const size_t slots = (size_t)n + 1;
+    if (int rc = ensure_buf(ctx->sd_meta, sizeof(int64_t) * slots + 64)) return rc;
+    if (int rc = ensure_buf(ctx->si_frames, sizeof(flacmi_frame_info) * slots)) return rc;
+    if (int rc = ensure_buf(ctx->si_subs, sizeof(flacmi_subframe_info) * slots * ch)) return rc;
+    if (int rc = ensure_buf(ctx->si_parts, slots * ch * ps + 16)) return rc;
+    int64_t* d_off = (int64_t*)ctx->sd_meta.p;
+    flacmi_frame_info* d_fi = (flacmi_frame_info*)ctx->si_frames.p;
+    flacmi_subframe_info* d_si = (flacmi_subframe_info*)ctx->si_subs.p;
+    uint8_t* d_pp = (uint8_t*)ctx->si_parts.p;
+    std::vector<flacmi_frame_info> fi((size_t)n);
+    std::vector<flacmi_subframe_info> si((size_t)n * ch);
+    std::vector<uint8_t> pp((size_t)n * ch * ps);
+    std::vector<int32_t> st1((size_t)n);
+    std::vector<int64_t> end1((size_t)n);
+    /* a parsed frame's end is its own, not the next candidate's offset: a word that is no
+     * reference exception makes the walk read frame_end */
+    constexpr int32_t kParsed = (FLACMI_DSITE_FRAME_END << 16) | FLACMI_STATUS_VERIFY;
+    if (n) {
+        std::vector<int64_t> off((size_t)n);
+        for (int64_t k = 0; k < n; ++k) off[k] = table[k].offset;
+        HIP_TRY(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        if (int rc = flacmi_frame_info_device(ctx, d_data, bytes, d_off, n, dp, d_fi, d_si, d_pp, part_stride, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(fi.data(), d_fi, sizeof(flacmi_frame_info) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(si.data(), d_si, sizeof(flacmi_subframe_info) * (size_t)n * ch, hipMemcpyDeviceToHost, s));
+        if (!pp.empty()) HIP_TRY(hipMemcpyAsync(pp.data(), d_pp, pp.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s)); /* off is a local vector */
+        for (int64_t k = 0; k < n; ++k) {
+            st1[k] = fi[k].status ? fi[k].status : kParsed;
+            end1[k] = fi[k].end;
+        }
+    }
+
+    /* 5. the walk; a probe parses the one frame at w.pos into slot n */
+    struct Probed {
+        flacmi_frame_info fi;
+        std::vector<flacmi_subframe_info> si;
+        std::vector<uint8_t> pp;
+    };
+    std::map<int64_t, Probed> probed; /* by offset */
+    std::vector<flacmi_chain_frame> chain((size_t)n + 16);
+    flacmi_walk w{};
+    w.pos = first_byte;
+    for (;;) {
+        if (int rc = flacmi_host_chain_walk(table.data(), n, st1.data(), end1.data(), bytes, final_chunk, &w, chain.data(),
+                                            (int64_t)chain.size()))
+            return rc;
+        if (w.state == FLACMI_WALK_FULL) {
+            chain.resize(chain.size() * 2);
+            w.state = FLACMI_WALK_RUN;
+            continue;
+        }
+        if (w.state != FLACMI_WALK_PROBE) break;
+        if ((int64_t)chain.size() == w.n_chain) chain.resize(chain.size() * 2);
+        Probed& q = probed[w.pos];
+        q.si.resize(ch);
+        q.pp.resize(ch * ps);
+        const int64_t at = w.pos;
+        HIP_TRY(hipMemcpyAsync(d_off + n, &at, sizeof(at), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s)); /* `at` is a local */
+        if (int rc = flacmi_frame_info_device(ctx, d_data, bytes, d_off + n, 1, dp, d_fi + n, d_si + (size_t)n * ch,
+                                              d_pp + (size_t)n * ch * ps, part_stride, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(&q.fi, d_fi + n, sizeof(flacmi_frame_info), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(q.si.data(), d_si + (size_t)n * ch, sizeof(flacmi_subframe_info) * ch, hipMemcpyDeviceToHost, s));
+        if (!q.pp.empty()) HIP_TRY(hipMemcpyAsync(q.pp.data(), d_pp + (size_t)n * ch * ps, q.pp.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        w.probe_status = q.fi.status;
+        w.probe_end = q.fi.end;
+        ++res->probes;
+    }
+    int64_t nc = w.n_chain;
+    int32_t stop = w.state == FLACMI_WALK_STOPPED ? w.stop_status : 0;
+    if (nc > frame_capacity) { /* ends the call like a cut-off frame */
+        nc = frame_capacity;
+        stop = 0;
+        res->full = 1;
+        w.pos = chain[nc].offset;
+    }
+
+    /* 6. the chain frames' records, in stream order */
+    for (int64_t i = 0; i < nc; ++i) {
+        const flacmi_chain_frame& c = chain[i];
+        const flacmi_frame_info* f1;
+        const flacmi_subframe_info* s1;
+        const uint8_t* p1;
+        if (c.candidate >= 0) {
+            f1 = &fi[c.candidate];
+            s1 = si.data() + (size_t)c.candidate * ch;
+            p1 = pp.data() + (size_t)c.candidate * ch * ps;
+        } else {
+            auto it = probed.find(c.offset);
+            if (it == probed.end()) return fail(FLACMI_E_INVALID, "internal: chain frame without a record");
+            f1 = &it->second.fi;
+            s1 = it->second.si.data();
+            p1 = it->second.pp.data();
+        }
+        frame_info[i] = *f1;
+        memcpy(subframe_info + (size_t)i * ch, s1, sizeof(flacmi_subframe_info) * ch);
+        if (ps) memcpy(part_params + (size_t)i * ch * ps, p1, ch * ps);
+    }
+    res->frames = nc;
     res->consumed = w.pos;
     res->status = stop & 0xFFFF;
     res->site = (stop >> 16) & 0xFFFF;

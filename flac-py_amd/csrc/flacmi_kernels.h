@@ -222,6 +222,21 @@ __host__ __device__ inline bool parse_header(const uint8_t* s, int64_t bytes, in
     return true;
 }
 
+/* Stream report (k_info.hip, k_frame_info): one lane per frame start, the parse of
+ * decode_general with nothing restored and every field it read written out. */
+struct InfoArgs {
+    const uint32_t* words;   /* stream bytes (4-byte aligned) */
+    int64_t stream_bytes, n_words;
+    const int64_t* offsets;  /* [n_frames] frame starts */
+    int64_t n_frames;
+    int32_t channels, sample_size;
+    flacmi_frame_info* frames;   /* [n_frames] */
+    flacmi_subframe_info* subs;  /* [n_frames][channels] */
+    uint8_t* parts;              /* [n_frames][channels][part_stride], or nullptr */
+    int32_t part_stride;
+    const uint16_t* crc_slice;   /* [4][256] CRC-16 slice-by-4 tables */
+};
+
 /* PCM writer (k_index.hip, k_pcm) */
 struct PcmArgs {
     const flacmi_pcm_frame* frames;
@@ -243,7 +258,7 @@ ResidLaunch resid_launch_config(int n, int rmax_eff, int residual_bytes);
 constexpr int kMaxFinestParts = 4096;
 
 /* flacmi_set_knob's knobs: the environment's value (read once) or the last value set */
-enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobEnergyBound, kKnobCount };
+enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobEnergyBound, kKnobInfoGrid, kKnobCount };
 int knob(Knob k);
 
 hipError_t launch_lpc(const LpcArgs& a, hipStream_t s);
@@ -285,6 +300,8 @@ int64_t frame_scan_blocks(int64_t n_frames);
 hipError_t launch_pack(const FrameArgs& a, hipStream_t s);
 hipError_t launch_decode(DecodeArgs a, hipStream_t s);
 hipError_t launch_index(const IndexArgs& a, hipStream_t s);
+/* grid_cap: workgroups (of 64 frames) at most, 0 = the default */
+hipError_t launch_frame_info(const InfoArgs& a, int grid_cap, hipStream_t s);
 int64_t index_scan_groups(int64_t n_tiles);
 hipError_t launch_pcm(const PcmArgs& a, hipStream_t s);
 

@@ -51,7 +51,7 @@ extern "C" {
       and see no change
    5: flacmi_params.reserved[1] takes FLACMI_FLAG_LPC_SIGN (the corrected LPC predictor sign, off by
       default); version 4 callers never set bit 2 there and see no change */
-#define FLACMI_ABI_VERSION 5
+#define FLACMI_ABI_VERSION 6
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
                                         code); analysis returns FLACMI_E_UNSUPPORTED where a block's
@@ -616,6 +616,96 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
                               uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
                               flacmi_stream_result* res);
 
+/* ---- stream analysis: what a .flac holds, frame by frame (flac-py README, known issue 3) -- */
+/* The reference has no such tool ("It would be nice to have a tool providing information
+ * about a FLAC file, as `flac -a` does").  k_frame_info walks a frame exactly as get_frame
+ * does (decoder.py:111-130, :133-262, :267-421) and reports what it read instead of restoring
+ * samples.  It takes frame starts only: the frame ends where the parse stops.
+ *
+ * status = (site << 16) | status from the decoder's catalogue (flacmi_decode_site), but only
+ * the exceptions get_frame itself raises, and EOFError: a negative LPC shift is reported in
+ * `shift`, not as FLACMI_DSITE_NEG_SHIFT (_decode_prediction raises that, after get_frame),
+ * and no verifier finding exists here: both CRCs are always computed and reported beside the
+ * stored ones, a mismatch is a fact of the stream.  The decoder's two documented choices hold
+ * (above FLACMI_STATUS_EOF): an L_R frame holds dp->channels subframes, wasted bits are
+ * counted, not applied.  Sample-rate code 11 reports 96000 (the reference's table lacks the
+ * entry: common.py:149-161). */
+typedef struct flacmi_frame_info {
+    int64_t offset;            /* the frame's first byte (frame_offsets[f]) */
+    int64_t end;               /* the byte after the CRC-16, or -1: the parse raised */
+    int64_t coded_number;      /* coded_number.py:45-70 */
+    int32_t status;            /* 0, or (site << 16) | status of the exception get_frame raises */
+    int32_t block_size;
+    int32_t blocking_strategy; /* 0 fixed, 1 variable */
+    int32_t sample_rate;       /* Hz as decoder.py:157-167 yields it; 0: from STREAMINFO */
+    int32_t sample_size;       /* bits; 0: from STREAMINFO */
+    int32_t channel_code;      /* 0..7 independent channels - 1, 8 L_S, 9 S_R, 10 M_S */
+    int32_t n_subframes;       /* subframes fully parsed */
+    int32_t header_bytes;      /* CRC-8 byte included */
+    int32_t crc8_stored, crc8_computed;   /* crc.py:18-22 over the header */
+    int32_t crc16_stored, crc16_computed; /* crc.py:25-31 over [offset, end - 2); 0, 0 when end is -1 */
+    int32_t padding_bits;      /* zero bits between the last subframe and the CRC-16 */
+    int32_t reserved0;
+} flacmi_frame_info;
+enum flacmi_subframe_type { FLACMI_SUB_TYPE_CONSTANT = 0, FLACMI_SUB_TYPE_VERBATIM = 1, FLACMI_SUB_TYPE_FIXED = 2,
+                            FLACMI_SUB_TYPE_LPC = 3 };
+typedef struct flacmi_subframe_info {
+    int64_t bit_offset;        /* of the subframe's padding bit, from the frame's first bit */
+    int64_t bits;              /* the subframe's total size */
+    int32_t type;              /* flacmi_subframe_type */
+    int32_t order;             /* predictor order (0 for CONSTANT / VERBATIM) */
+    int32_t wasted_bits;
+    int32_t sample_bits;       /* the width read: stream size + decorrelation bit - wasted */
+    int32_t precision;         /* LPC: coefficient width in bits (the field + 1), else 0 */
+    int32_t shift;             /* LPC: signed, as read; else 0 */
+    int16_t coefficients[32];  /* LPC: the first `order`, the rest 0; all 0 otherwise */
+    int32_t coding_method;     /* Rice parameter width: 4, 5, or 0 for none */
+    int32_t partition_order;
+    int32_t escaped_partitions;
+    int32_t reserved0;
+    int64_t residual_bits;     /* from the coding-method field to the last code */
+    int64_t abs_sum;           /* sum |r| of the residual (what encode() compares, encoder.py:135-157) */
+    int64_t constant_value;    /* CONSTANT only */
+    int32_t partitions_stored; /* min(2^partition_order, part_stride) */
+    int32_t reserved1;
+} flacmi_subframe_info;
+/* All pointers are device pointers; the work is enqueued on `stream` (stream_data 4-byte
+ * aligned, readable up to the next multiple of 4 after stream_bytes).  frame_info[n_frames];
+ * subframe_info rows [n_frames][dp->channels]: of frame f the first min(n_subframes,
+ * dp->channels) records are written, the others left as they were (a header that declares
+ * more channels than dp->channels has the further subframes parsed and counted only).
+ * part_params[n_frames][dp->channels][part_stride] bytes (part_stride >= 0, NULL when 0): one
+ * byte per partition, the Rice parameter, or 0x80 | width for an escaped partition; of a
+ * subframe the first partitions_stored bytes are written, partitions at and beyond part_stride
+ * are parsed and counted but not stored.  dp->first_frame and dp->check_crc are not used. */
+int flacmi_frame_info_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
+                             const int64_t* frame_offsets, int64_t n_frames, const flacmi_decode_params* dp,
+                             flacmi_frame_info* frame_info, flacmi_subframe_info* subframe_info,
+                             uint8_t* part_params, int64_t part_stride, void* stream);
+
+/* One chunk of a stream, host bytes in, host records out (synchronous), the sibling of
+ * flacmi_decode_stream_host: copy in, k_index, k_frame_info over every candidate, the
+ * candidates' records out, flacmi_host_chain_walk over their status / end (a
+ * FLACMI_WALK_PROBE launches k_frame_info for the one offset), and the chain frames' records
+ * gathered into the caller's arrays in stream order: frame_info[frame_capacity],
+ * subframe_info[frame_capacity][dp->channels], part_params[frame_capacity][dp->channels]
+ * [part_stride] (host pointers).  first_byte / final_chunk / consumed as in the decode call: a
+ * frame the chunk cuts off ends the call with res->consumed at its start.  A frame that raises
+ * stops the stream: res->status / site, and its own record is not delivered. */
+typedef struct flacmi_info_result {
+    int64_t frames;          /* frames delivered */
+    int64_t consumed;        /* offset after the last delivered frame */
+    int32_t status, site;    /* why the stream stopped: 0, 0 = it has not */
+    int64_t candidates;      /* k_index's count */
+    int64_t probes;          /* starts that were no candidate, parsed one by one */
+    int64_t full;            /* 1: frame_capacity reached; call again from `consumed` */
+    int64_t reserved0;
+} flacmi_info_result;
+int flacmi_info_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                            const flacmi_decode_params* dp, int32_t final_chunk, flacmi_frame_info* frame_info,
+                            flacmi_subframe_info* subframe_info, uint8_t* part_params, int64_t part_stride,
+                            int64_t frame_capacity, flacmi_info_result* res);
+
 /* ---- stream statistics (reduced across GPUs with one RCCL all-reduce) ------------- */
 #define FLACMI_STATS_WORDS 128
 /* stats[0] units, [1] samples, [2] rice bits, [3] fixed units, [4] lpc units,
@@ -703,7 +793,9 @@ int flacmi_timing_reset(flacmi_ctx* ctx);
  * (0 = no second fast-decoder pass for LPC subframes: those frames go to the general decoder
  * kernel; default 1), "FLACMI_ENERGY_BOUND" (the stream kernel's pruning calls: 1 = prove LPC's
  * loss from the autocorrelation first, then the partial-sum tiers (default); 0 = the tiers
- * alone; 2 = that proof, then the exact sums; same results but for meta.lpc_tiers).
+ * alone; 2 = that proof, then the exact sums; same results but for meta.lpc_tiers),
+ * "FLACMI_INFO_GRID" (cap on k_frame_info's grid in workgroups of 64 frames, 0 = the default
+ * 2048; tests force a grid-stride loop with it).
  * FLACMI_E_INVALID for any other name.  No device needed. */
 int flacmi_set_knob(const char* name, int32_t value);
 int flacmi_get_knob(const char* name, int32_t* value);
