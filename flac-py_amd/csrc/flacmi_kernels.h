@@ -38,7 +38,13 @@ struct LpcArgs {
 /* the energy bound: the word pair of a unit it must not decide, and the lags
  * k = 1 .. kBoundLags of kappa_k = max_i |w_i - w_{i-k}| stored at window[n + kWindowPad ..] */
 constexpr uint32_t kBoundUnusable = 0xffffffffu;
+/* second word of an unusable pair: some order's sum|taps| exceeds kCoefLimit (below), so the
+ * stream kernel will list the unit and need not run its fixed group first */
+constexpr uint32_t kBoundOutside = 0xfffffffeu;
 constexpr int kBoundLags = 13;
+/* k_resid_stream's MFMA exactness bound per LPC order: (sum|c| + 2^shift) * 33023 < 2^22.  A
+ * unit outside it is listed by the stream kernel; k_lpc gives it unusable bound words */
+constexpr int kCoefLimit = 127;
 
 struct ResidArgs {
     const void* samples;

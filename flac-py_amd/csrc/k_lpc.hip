@@ -37,7 +37,16 @@ __device__ __forceinline__ void write_quant(int32_t* rec, int L, int p, const in
  *   U2_p = sum_j |c_j| / 2^s kappa_{j+1}, kappa_k = max_i |w_i - w_{i-k}| (behind the
  *          window's zero pad).
  * Words: ceil(sqrt(n max_p E_p)) + 1 and ceil(256 max_p U2_p) + 1, or kBoundUnusable twice
- * for a unit with a status, a negative-shift order or a value that is not finite. */
+ * for a unit with a status, a negative-shift order or a value that is not finite, and for a
+ * unit the stream kernel lists: max_p sum|a_p| > kCoefLimit.  The stream kernel runs its
+ * pre-test before it looks at a coefficient, and a listed unit must reach its own test (it
+ * reports exact LPC values from the list kernel, never FLACMI_LPC_PRUNED).  sum|a| here is an
+ * exact integer; the stream kernel sums the same |taps| as f16 halves in f32: a half is exact
+ * for |v| <= 2048, a larger tap rounds to >= 2048 or to inf, and non-negative f32 sums of such
+ * terms are exact below 2^24, so its test is true exactly when this sum exceeds kCoefLimit.
+ * The pair's second word then is kBoundOutside: the stream kernel skips its fixed group for
+ * such a unit (a listed unit's sums come from the list kernel) and goes straight to its own
+ * test, which stays the one that lists. */
 template <int LMAX, bool EB = false>
 __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const LpcArgs& a, int32_t* __restrict__ rec,
                                            uint32_t* __restrict__ bound = nullptr) {
@@ -45,7 +54,7 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
     const bool eb = EB && bound != nullptr; /* wave-uniform */
     const __attribute__((address_space(4))) double* kap =
         (const __attribute__((address_space(4))) double*)a.window + a.n + kWindowPad - 1; /* kap[k], k = 1 .. 13 */
-    double emax = 0.0, u2max = 0.0;
+    double emax = 0.0, u2max = 0.0, samax = 0.0;
     bool ebad = false;
     const pym::PowTables PT{c_log_hdr, c_log_tab, c_exp_hdr, c_exp_tab};
     double c[LMAX + 1];
@@ -159,6 +168,7 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
                                         sa = sa + __builtin_fabs(aq[l]);
                                         if (l > 0) u2 = __builtin_fma(__builtin_fabs(aq[l]), kap[l], u2);
                                     }
+                                    samax = sa > samax ? sa : samax; /* sum|a|: an exact integer */
                                     sa = sa * inv;
                                     en = en * inv * inv + sa * sa * acc[0] * 0x1p-39;
                                     u2 = u2 * inv;
@@ -185,8 +195,11 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
         if (eb) {
             const double u1 = __builtin_ceil(__builtin_sqrt((double)a.n * emax) * (1.0 + 0x1p-40)) + 1.0;
             const double u2 = __builtin_ceil(256.0 * u2max * (1.0 + 0x1p-40)) + 1.0;
-            const bool ok = st == ST_OK && negmask == 0 && !ebad && u1 < 4294967295.0 && u2 < 4294967295.0;
-            *reinterpret_cast<uint2*>(bound) = ok ? uint2{(uint32_t)u1, (uint32_t)u2} : uint2{kBoundUnusable, kBoundUnusable};
+            const bool ok = st == ST_OK && negmask == 0 && !ebad && samax <= (double)kCoefLimit && u1 < 4294967295.0 &&
+                            u2 < 4294967295.0;
+            const bool out = st == ST_OK && samax > (double)kCoefLimit;
+            *reinterpret_cast<uint2*>(bound) =
+                ok ? uint2{(uint32_t)u1, (uint32_t)u2} : uint2{kBoundUnusable, out ? kBoundOutside : kBoundUnusable};
         }
     }
 }

@@ -66,7 +66,6 @@ __host__ __device__ constexpr int stream_threads(int n) {
 }
 constexpr int kSHP = 16;                     /* biased-zero history pad in front of the unit (samples) */
 constexpr uint32_t kMagicBits = 0x4B400000u; /* 1.5 * 2^23 */
-constexpr int kCoefLimit = 127;              /* (sum|c| + 2^shift) * 33023 < 2^22 */
 constexpr int kRiceOrders = 8;               /* orders 0..7 kept per finest partition */
 
 struct SLds {
@@ -328,15 +327,18 @@ __device__ __forceinline__ void store_meta(flacmi_unit_meta* m, int lane, const 
  * EB (batch kernel, NG > 0, a.prune): the energy bound's pre-test.  The fixed group
  * runs over every block first; then 2 W - 256 (U1 + n) - U2 F0 > 256 fmin, from k_lpc's two words
  * (U1, U2), the exact order-0 sum F0 and W = sum_chunks weight * sum_chunk |x| gathered in
- * staging, proves that every LPC order loses, and no LPC group runs at all.  An undecided
- * unit runs tier 0 as a loop of its own, then the tiers as before (a.energy == 2: the exact
- * pass at once). */
+ * staging, proves that every LPC order loses, and no LPC group runs at all.  Nothing of the
+ * LPC record but its status word is read before the pre-test: only an undecided unit builds the
+ * tap table and the LPC operands and takes the exactness test (k_lpc marks every unit that test
+ * lists unusable, so none is decided first), then runs tier 0 as a loop of its own and the
+ * tiers as before (a.energy == 2: the exact pass at once). */
 template <int NG, bool R05, int NFIX, bool LIST, bool EB, typename Args>
 __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, unsigned char* smem) {
     /* NFIX: the block length (and L = 4 NG, the workgroup size) as compile-time constants, the
      * BASELINE configs' 4608-sample units: loop bounds, chunk guards and partition indices fold */
     /* LIST: the thread id through an opaque register per unit (hoisted out of the unit loop,
      * every value derived from it would stay live across the whole body) */
+    static_assert(!EB || (NG > 0 && !LIST), "the energy bound's build is the batch kernel's, in reference mode");
     const int tid = LIST ? (int)opaque((uint32_t)threadIdx.x) : (int)threadIdx.x, NT = NFIX ? stream_threads(NFIX) : (int)blockDim.x, lane = tid & 63, nw = NT >> 6;
 #if FLACMI_STREAM_STAMPS /* diagnostic build only: per-unit phase clock stamps of wave 0 */
     uint64_t stamp[8];
@@ -366,7 +368,9 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
     flacmi_unit_meta* meta = a.meta + gid;
     MetaVals mv{};
 
-    /* ---- stage: biased samples and the record into LDS, sum|x| on the way ---- */
+    /* ---- stage: biased samples and the record into LDS, sum|x| on the way (EB: no record
+     * here; a unit its pre-test does not decide builds the tap table then) ---- */
+    constexpr int kTW = tap_table_words(NG), kTJ = NG > 0 ? (kTW + 63) / 64 : 0;
     uint4 fixb; /* the fixed group's MFMA B operand (constant) */
     {
         const uint4* src = reinterpret_cast<const uint4*>((const int16_t*)a.samples + (a.unit0 + gid) * a.stride);
@@ -391,9 +395,8 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         }
         /* tap table words tid + j NT: word w of row p holds (T_p[16 - 2w], T_p[15 - 2w]); the
          * record values it needs are loaded here, with the samples (clamped, unconditional) */
-        constexpr int kTW = tap_table_words(NG), kTJ = NG > 0 ? (kTW + 63) / 64 : 0;
         int32_t tv[kTJ > 0 ? kTJ : 1][2];
-        if constexpr (NG > 0) {
+        if constexpr (NG > 0 && !EB) {
             const int32_t* r = a.rec + gid * rw;
 #pragma unroll
             for (int j = 0; j < kTJ; ++j) {
@@ -444,7 +447,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                 }
             }
         }
-        if constexpr (NG > 0) {
+        if constexpr (NG > 0 && !EB) {
             uint32_t* tt = reinterpret_cast<uint32_t*>(recl);
 #pragma unroll
             for (int j = 0; j < kTJ; ++j) {
@@ -483,8 +486,14 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
             }
             return;
         }
-        negmask = (uint32_t)grec[1];
+        if constexpr (!EB) negmask = (uint32_t)grec[1]; /* (EB: with the rest of the record, once undecided) */
     }
+    /* EB: k_lpc's two words (wave-uniform: a scalar load).  listed: k_lpc found the unit outside the
+     * MFMA bound, so it will be listed below and its fixed sums would be thrown away: the fixed
+     * group is skipped */
+    uint2 bw{0u, 0u};
+    if constexpr (EB) bw = *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
+    const bool listed = EB && bw.x == kBoundUnusable && bw.y == kBoundOutside;
 
     /* ---- candidate sums on MFMA ----
      * Exact mode: every block runs all NG + 1 groups and the LPC values are exact
@@ -497,7 +506,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
      * sum for every order, LPC loses strictly (encoder.py:135-157: no win, no tie) and its
      * exact sums are never needed.  Otherwise the LPC groups run again, exact, over every
      * block (a workgroup-uniform branch: every wave decides from the same LDS words). */
-    const bool prune = NG > 0 && a.prune && !LIST;
+    const bool prune = EB || (NG > 0 && a.prune && !LIST); /* (the host launches the EB build for pruning calls only) */
     unsigned long long* red64 = reinterpret_cast<unsigned long long*>(smem + lay.red); /* [nw][4 groups][4 orders] */
     auto lane_total = [&](bool with_lpc = true) __attribute__((always_inline)) -> uint64_t {
         /* lanes 1..4: fixed orders 1..4, lane 0: order 0 (sum|x|), lanes 16..15+4NG: LPC orders */
@@ -534,8 +543,9 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         const int k0 = 4 + 4 * kb - rho; /* 16 - ia */
         const uint32_t alb = 16u * (uint32_t)(k0 & 1);
         bool outside = false;
+        /* (EB: the fixed group's operand alone; the LPC groups' below, once undecided) */
 #pragma unroll
-        for (int g = 0; g <= NG; ++g) {
+        for (int g = 0; g <= (EB ? 0 : NG); ++g) {
             int sh = 0;
             if (g == 0) {
                 B[0] = __builtin_bit_cast(h8, fixb);
@@ -568,7 +578,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
             }
             shg[g] = sh;
         }
-        if (NG > 0 && __ballot(outside)) {
+        if (NG > 0 && !EB && __ballot(outside)) {
             /* outside the MFMA exactness bound: the list kernel (pred-only taps) redoes it, and a
              * unit outside that bound too goes to k_resid's list variant */
             if (tid == 0) {
@@ -685,9 +695,11 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         const int kw = (nblk - wid + nw - 1) / nw;
         if (EB && prune) {
             /* the fixed group alone over every block: the pre-test below needs the fixed sums */
-            for (int k = wid == 0 ? 1 : 0; k < kw; ++k) blockA(I0{}, I0{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
-            if (wid == 0) block(I0{}, I0{}, I0{}, ld0(), true, 0);
-            reduce_store(I0{}, I0{}, I0{});
+            if (!listed) {
+                for (int k = wid == 0 ? 1 : 0; k < kw; ++k) blockA(I0{}, I0{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
+                if (wid == 0) block(I0{}, I0{}, I0{}, ld0(), true, 0);
+                reduce_store(I0{}, I0{}, I0{});
+            }
         } else if (prune) {
             /* tier 0: the wave's blocks k % 4 == 0 run the LPC groups (bound) beside the fixed
              * group; tiers 1..3 (only while the bound has not decided) add k % 4 == 2, 1, 3 */
@@ -705,9 +717,11 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
             reduce_store(I0{}, I0{}, ING{});
             if constexpr (LIST) mv.tiers = 1 | (1 << 8); /* one exact pass (the listed units' marker) */
         }
-        __syncthreads(); /* B2 */
-        STAMP(3);
-        tj = lane_total(!(EB && prune));
+        if (!listed) { /* (workgroup-uniform; a listed unit has no sums to exchange) */
+            __syncthreads(); /* B2 */
+            STAMP(3);
+            tj = lane_total(!(EB && prune));
+        }
         if constexpr (NG > 0) {
             if (prune) {
                 /* best fixed sum (exact) against every LPC order's lower bound */
@@ -726,7 +740,6 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                     uint64_t wr = 0;
 #pragma unroll 1
                     for (int w2 = 0; w2 < nw; ++w2) wr += red0[nw + w2];
-                    const uint2 bw = *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
                     const uint64_t f0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tj >> 32), 0) << 32) |
                                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tj, 0);
                     const uint64_t rhs = 256ull * ((uint64_t)bw.x + (uint64_t)n + fmin) + (uint64_t)bw.y * f0;
@@ -734,16 +747,81 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                         pruned = true;
                         tiers = false;
                         mv.tiers = 1 | (4 << 8);
-                    } else if (a.energy == 2) {
-                        tiers = false; /* (tests, hit-rate counts) straight to the exact pass */
                     } else {
-                        /* tier 0 after all: the LPC groups (bound) over the wave's blocks k % 4 == 0,
-                         * the masked block 0 among them; their red64 slots are not the fixed group's */
-                        for (int k = wid == 0 ? 4 : 0; k < kw; k += 4) blockA(I1{}, ING{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
-                        if (wid == 0) block(I1{}, ING{}, I0{}, ld0(), true, 0);
-                        reduce_store(I1{}, I1{}, ING{});
-                        __syncthreads();
-                        tj = lane_total();
+                        /* Undecided: only now the LPC setup that the other builds do in staging and
+                         * before their loop (the same steps, kept apart from them: shared lambdas
+                         * changed the other builds' register allocation).  Record words -> the tap
+                         * table (its LDS region is free until the Rice table, after B3), one barrier,
+                         * then the operands, the shifts and the exactness test.  k_lpc gives every unit
+                         * this test lists unusable words, so none was decided above: such a unit is
+                         * listed here as it was before the loop. */
+                        {
+                            const int32_t* r = a.rec + gid * rw;
+                            uint32_t* tw = reinterpret_cast<uint32_t*>(recl);
+                            int32_t tv[kTJ > 0 ? kTJ : 1][2];
+#pragma unroll
+                            for (int j = 0; j < kTJ; ++j) {
+                                if (j > 0 && j * NT >= kTW) break; /* uniform */
+                                const int gw = tid + j * NT, p = gw / 10 + 1, w = gw - 10 * (p - 1);
+                                const int pc = p < L ? p : L, base = 2 + L + (pc * (pc - 1)) / 2;
+                                tv[j][0] = r[w == 8 ? 1 + pc : min(max(base + 15 - 2 * w, 0), rw - 1)];
+                                tv[j][1] = r[min(max(base + 14 - 2 * w, 0), rw - 1)];
+                            }
+                            negmask = (uint32_t)grec[1];
+#pragma unroll
+                            for (int j = 0; j < kTJ; ++j) {
+                                if (j > 0 && j * NT >= kTW) break;
+                                const int gw = tid + j * NT, p = gw / 10 + 1, w = gw - 10 * (p - 1);
+                                if (gw < kTW) {
+                                    auto tap = [&](int i, int32_t c) -> uint32_t {
+                                        if (p > L || i < 0 || i > p) return 0u;
+                                        return f16_of_int(i == 0 ? -(1 << c) : c);
+                                    };
+                                    tw[gw] = tap(16 - 2 * w, tv[j][0]) | tap(15 - 2 * w, tv[j][1]) << 16;
+                                }
+                            }
+                        }
+                        __syncthreads(); /* the tap table is whole */
+#pragma unroll
+                        for (int g = 1; g <= NG; ++g) {
+                            const int p = 4 * (g - 1) + o4 + 1, wb = 10 * (p - 1) + (k0 >> 1);
+                            const uint32_t w0 = tt[wb], w1 = tt[wb + 1], w2 = tt[wb + 2];
+                            const uint32_t l0 = __builtin_amdgcn_alignbit(w1, w0, alb), l2 = __builtin_amdgcn_alignbit(w2, w1, alb);
+                            const h2 k256{(_Float16)256.0f, (_Float16)256.0f};
+                            const uint32_t h0 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, l0) * k256);
+                            const uint32_t hh = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h2, l2) * k256);
+                            B[g] = __builtin_bit_cast(h8, uint4{h0, hh, l0, l2});
+                            const h2 one{(_Float16)1.0f, (_Float16)1.0f};
+                            float sw = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, l0 & 0x7fff7fffu), one, 0.0f, false);
+                            sw = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, l2 & 0x7fff7fffu), one, sw, false);
+                            sw += __shfl_xor(sw, 16);
+                            sw += __shfl_xor(sw, 32);
+                            outside |= rho == 0 && p <= L && sw > (float)kCoefLimit;
+                            const uint32_t t0 = tt[10 * (p - 1) + 8] & 0xffffu;
+                            shg[g] = p <= L ? (int)((t0 >> 10) & 31u) - 15 : 0;
+                        }
+                        /* (listed without outside cannot happen, see k_lpc's lpc_finish; the unit has no
+                         * fixed sums, and the list kernel computes any unit exactly) */
+                        if (__ballot(outside) || listed) {
+                            if (tid == 0) { /* sub-list gid & 63, as above */
+                                meta->status = FLACMI_STATUS_RETRY;
+                                const int r = (int)(gid & 63);
+                                const unsigned long long k = atomicAdd(a.retry_sub + 16 * r, 1ull);
+                                a.retry_list[r * a.retry_sub_cap + (int64_t)k] = gid;
+                            }
+                            return;
+                        }
+                        if (a.energy == 2) {
+                            tiers = false; /* (tests, hit-rate counts) straight to the exact pass */
+                        } else {
+                            /* tier 0 after all: the LPC groups (bound) over the wave's blocks k % 4 == 0,
+                             * the masked block 0 among them; their red64 slots are not the fixed group's */
+                            for (int k = wid == 0 ? 4 : 0; k < kw; k += 4) blockA(I1{}, ING{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
+                            if (wid == 0) block(I1{}, ING{}, I0{}, ld0(), true, 0);
+                            reduce_store(I1{}, I1{}, ING{});
+                            __syncthreads();
+                            tj = lane_total();
+                        }
                     }
                 }
 #pragma unroll 1
