@@ -75,6 +75,8 @@ FLAG_LPC_SIGN = 4  # params.reserved[1]: the corrected LPC predictor sign (negat
 LPC_PRUNED = -1          # meta.lpc_order / lpc_sum of a unit whose LPC candidates were pruned
 FRAME_FALLBACK = 1       # flacmi_frame_params.reserved0 (flacmi_frame_flags): CONSTANT / VERBATIM fallback subframes
 SUB_ANALYSED, SUB_CONSTANT, SUB_VERBATIM = 0, 1, 2  # flacmi_sub_kind: sub_kind[u] of the fallback mode
+FRAME_WASTED = 4         # flacmi_frame_params.reserved0: wasted-bits subframes (flacmi_encode_host / _pipeline)
+DECODE_WASTED_SPEC = 1   # flacmi_decode_params.reserved0 (flacmi_decode_flags): wasted bits as the format codes them
 STEREO_OFF, STEREO_BEST = 0, 1  # flacmi_frame_params.reserved[1] (flacmi_stereo_mode): stereo decorrelation
 CHANNELS_L_R, CHANNELS_L_S, CHANNELS_S_R, CHANNELS_M_S = 1, 8, 9, 10  # a stereo frame's channel assignment code
 
@@ -374,6 +376,8 @@ SIGNATURES = {
     "flacmi_encode_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "flacmi_stereo_rows_device": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_int64, C.c_void_p]),
+    "flacmi_wasted_rows_device": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p]),
     "flacmi_encode_pipeline": (C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Params), C.POINTER(FrameParams),
                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.POINTER(EncodeTiming)]),

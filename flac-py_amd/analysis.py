@@ -36,14 +36,17 @@ def make_params(max_lpc_order: int, qlp_precision: int, rice_min: int, rice_max:
 
 
 def frame_params(channels: int, sample_size: int, qlp_precision: int, first_frame: int = 0,
-                 fallback: bool = False, sub_kind_ptr: int = 0, stereo: bool = False) -> abi.FrameParams:
+                 fallback: bool = False, sub_kind_ptr: int = 0, stereo: bool = False,
+                 wasted: bool = False) -> abi.FrameParams:
     """fallback: FLACMI_FRAME_FALLBACK (a unit the reference cannot write, or writes larger than
     raw, becomes a CONSTANT / VERBATIM subframe); sub_kind_ptr: the device int32 [n_units] array
     the *_device entry points then need (the host entry points keep their own).  stereo:
     FLACMI_STEREO_BEST (each two-channel frame takes the smallest of L_R, L_S, S_R, M_S; the host
-    entry points only)."""
+    entry points only).  wasted: FLACMI_FRAME_WASTED (a unit whose samples share w zero low bits is
+    written as x >> w at sample_size - w bits behind a header that declares w; the host entry points
+    only, not together with stereo)."""
     fp = abi.FrameParams()
-    fp.reserved0 = abi.FRAME_FALLBACK if fallback else 0
+    fp.reserved0 = (abi.FRAME_FALLBACK if fallback else 0) | (abi.FRAME_WASTED if wasted else 0)
     fp.reserved[0] = sub_kind_ptr
     fp.reserved[1] = abi.STEREO_BEST if stereo else abi.STEREO_OFF
     fp.channels = channels
@@ -222,9 +225,9 @@ class Analyzer:
     def encode_frames(self, samples: np.ndarray, params: abi.Params, block_len: int, tail_len: int = 0,
                       n_tail_units: int = 0, sample_bits: int = 16, channels: int = 1,
                       sample_size: int = 16, first_frame: int = 0, fallback: bool = False,
-                      stereo: bool = False):
+                      stereo: bool = False, wasted: bool = False):
         """Host rows in -> (frame bytes, frame offsets [n_frames + 1], frame status [n_frames]).
-        fallback, stereo: see frame_params.
+        fallback, stereo, wasted: see frame_params.
 
         Row f*channels + c is channel c of frame f.  A frame whose status is non-zero
         (the reference's exception, (site << 16) | status) has no bytes."""
@@ -241,7 +244,7 @@ class Analyzer:
         b.block_len = block_len
         b.tail_len = tail_len
         b.n_tail_units = n_tail_units
-        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback, stereo=stereo)
+        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback, stereo=stereo, wasted=wasted)
         n_frames = n_units // channels if channels else 0
         offsets = np.zeros(n_frames + 1, dtype=np.int64)
         status = np.zeros(max(n_frames, 1), dtype=np.int32)
@@ -255,7 +258,8 @@ class Analyzer:
     def encode_pipeline(self, samples: np.ndarray, params: abi.Params, block_len: int, tail_len: int = 0,
                         n_tail_units: int = 0, sample_bits: int = 16, channels: int = 1, sample_size: int = 16,
                         first_frame: int = 0, units_per_batch: int = 8192, capacity: int = 0,
-                        out: np.ndarray = None, fallback: bool = False, stereo: bool = False):
+                        out: np.ndarray = None, fallback: bool = False, stereo: bool = False,
+                        wasted: bool = False):
         """encode_frames through flacmi_encode_pipeline: host rows in (any row stride), the
         batch streamed through the device in sub-batches of units_per_batch units with the
         PCIe copies overlapping the kernels.  `out` (optional, uint8): the caller's frame
@@ -278,7 +282,7 @@ class Analyzer:
         b.block_len = block_len
         b.tail_len = tail_len
         b.n_tail_units = n_tail_units
-        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback, stereo=stereo)
+        fp = frame_params(channels, sample_size, params.qlp_precision, first_frame, fallback, stereo=stereo, wasted=wasted)
         n_frames = n_units // channels if channels else 0
         offsets = np.zeros(n_frames + 1, dtype=np.int64)
         status = np.zeros(max(n_frames, 1), dtype=np.int32)
@@ -348,6 +352,14 @@ class Analyzer:
                                                  stream),
               "flacmi_stereo_rows_device")
 
+    def wasted_rows_device(self, rows: abi.Batch, out_ptr: int, out_stride: int, wasted_ptr: int,
+                           stream: int = 0) -> None:
+        """flacmi_wasted_rows_device: wasted[u] (int32; 0 for an all-zero unit, else the count of
+        trailing zero bits of the OR of the unit's samples, at most sample_bits - 1) and the rows
+        shifted right by it, of a device batch.  out_ptr may be the batch's own rows."""
+        check(self.lib.flacmi_wasted_rows_device(self.ctx, C.byref(rows), out_ptr, out_stride, wasted_ptr, stream),
+              "flacmi_wasted_rows_device")
+
     # ------------------------------------------------------------------------------
     # decoder verifier (include/flacmi.h flacmi_decode_frames_device)
     # ------------------------------------------------------------------------------
@@ -362,10 +374,12 @@ class Analyzer:
 
     def decode_frames(self, data: np.ndarray, offsets: np.ndarray, channels: int, sample_size: int,
                       first_frame: int = -1, expect: np.ndarray = None, block_len: int = 0, tail_len: int = 0,
-                      n_tail_units: int = 0, out_stride: int = 0, check_crc: bool = True):
+                      n_tail_units: int = 0, out_stride: int = 0, check_crc: bool = True,
+                      spec_wasted_bits: bool = False):
         """Host bytes in -> (decoded int32 rows [n_frames*channels][out_stride], frame status,
         mismatches per frame), decoded on the device.  `expect` (int16/int32 rows of the
-        source units) turns on the in-kernel comparison."""
+        source units) turns on the in-kernel comparison.  spec_wasted_bits:
+        FLACMI_DECODE_WASTED_SPEC."""
         import torch
         dev = torch.device("cuda", self.device)
         n_frames = len(offsets) - 1
@@ -381,6 +395,7 @@ class Analyzer:
         mm = torch.zeros(max(n_frames, 1), dtype=torch.int64, device=dev)
         dp = abi.DecodeParams()
         dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, first_frame, int(check_crc)
+        dp.reserved0 = abi.DECODE_WASTED_SPEC if spec_wasted_bits else 0
         eb = None
         if expect is not None:
             e = torch.from_numpy(np.ascontiguousarray(expect)).to(dev)
@@ -448,10 +463,11 @@ class Analyzer:
 
     def decode_stream(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
                       check_crc: bool, max_block_size: int, final_chunk: bool, pcm_ptr: int, pcm_capacity: int,
-                      raw: bool, bytes_per_sample: int) -> abi.StreamResult:
+                      raw: bool, bytes_per_sample: int, spec_wasted_bits: bool = False) -> abi.StreamResult:
         """flacmi_decode_stream_host: one chunk of host stream bytes -> host PCM."""
         dp = abi.DecodeParams()
         dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, int(check_crc)
+        dp.reserved0 = abi.DECODE_WASTED_SPEC if spec_wasted_bits else 0
         res = abi.StreamResult()
         check(self.lib.flacmi_decode_stream_host(self.ctx, data_ptr, nbytes, first_byte, C.byref(dp), max_block_size,
                                                  int(final_chunk), pcm_ptr, pcm_capacity,
@@ -463,7 +479,7 @@ class Analyzer:
     # stream analysis (include/flacmi.h flacmi_frame_info_device / flacmi_info_stream_host)
     # ------------------------------------------------------------------------------
     def frame_info(self, data, offsets, channels: int, sample_size: int, part_stride: int = 64,
-                   sentinel: int = 0xEE):
+                   sentinel: int = 0xEE, spec_wasted_bits: bool = False):
         """Host bytes and frame starts in -> (FRAME_INFO_DTYPE [n], SUBFRAME_INFO_DTYPE [n][channels],
         part_params uint8 [n][channels][part_stride]) from k_frame_info.  The three arrays are
         filled with `sentinel` bytes first, so what the kernel did not write shows."""
@@ -482,6 +498,7 @@ class Analyzer:
         pp = filled(n * channels * part_stride)
         dp = abi.DecodeParams()
         dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, 0
+        dp.reserved0 = abi.DECODE_WASTED_SPEC if spec_wasted_bits else 0
         stream = torch.cuda.current_stream(dev).cuda_stream
         check(self.lib.flacmi_frame_info_device(self.ctx, buf.data_ptr(), nb, off.data_ptr(), n, C.byref(dp),
                                                 fi.data_ptr(), si.data_ptr(), pp.data_ptr() if part_stride else None,
@@ -493,12 +510,14 @@ class Analyzer:
                 pp.cpu().numpy()[:n * channels * part_stride].reshape(n, channels, part_stride))
 
     def info_stream(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
-                    final_chunk: bool, frames: np.ndarray, subframes: np.ndarray, parts: np.ndarray) -> abi.InfoResult:
+                    final_chunk: bool, frames: np.ndarray, subframes: np.ndarray, parts: np.ndarray,
+                    spec_wasted_bits: bool = False) -> abi.InfoResult:
         """flacmi_info_stream_host: one chunk of host stream bytes -> the records of its frames
         in frames [capacity] (FRAME_INFO_DTYPE), subframes [capacity][channels]
         (SUBFRAME_INFO_DTYPE) and parts [capacity][channels][part_stride] (uint8)."""
         dp = abi.DecodeParams()
         dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, 0
+        dp.reserved0 = abi.DECODE_WASTED_SPEC if spec_wasted_bits else 0
         res = abi.InfoResult()
         part_stride = parts.shape[2]
         assert subframes.shape == (len(frames), channels) and parts.shape[:2] == (len(frames), channels)

@@ -64,6 +64,9 @@ def make_argument_parser():
     enc.add_argument("--lpc-sign", action="store_true",
                      help="corrected LPC predictor sign: the LPC candidates predict x and not -x (the "
                           "reference's levinson_durbin returns the negated predictor)")
+    enc.add_argument("--wasted-bits", action="store_true",
+                     help="wasted-bits subframes: a block whose samples share w zero low bits (16-bit audio in a "
+                          "24-bit file) is written at w bits less a sample; read back with decode --spec-wasted-bits")
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
@@ -73,19 +76,24 @@ def make_argument_parser():
     dec.add_argument("--device", type=int, default=0)
     dec.add_argument("--check-crc", action="store_true",
                      help="verify the frames' CRC-8 and CRC-16 (the reference reads them unchecked)")
+    dec.add_argument("--spec-wasted-bits", action="store_true",
+                     help="read a subframe's wasted bits as the format codes them and shift them back in (the "
+                          "reference reads one too few and leaves the samples unshifted)")
     ana = action.add_parser("analyze", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     ana.add_argument("infile", type=Path, metavar="infile.flac")
     ana.add_argument("--partitions", action="store_true", help="list every subframe's Rice parameters")
     ana.add_argument("--json", action="store_true", help="one JSON object per line instead of key=value text")
     ana.add_argument("--summary-only", action="store_true", help="no metadata, frame and subframe lines")
     ana.add_argument("--device", type=int, default=0)
+    ana.add_argument("--spec-wasted-bits", action="store_true",
+                     help="report wasted bits and subframe sample widths as the format codes them")
     return parser
 
 
 def cmd_analyze(args) -> int:
     import json
     from . import info
-    report = info.analyze(args.infile, device=args.device)
+    report = info.analyze(args.infile, device=args.device, spec_wasted_bits=args.spec_wasted_bits)
     out = sys.stdout
     if not args.summary_only:
         if args.json:
@@ -126,7 +134,8 @@ def cmd_analyze(args) -> int:
 
 def cmd_decode(args) -> None:
     from .decoder import decode_wav
-    seconds = decode_wav(args.infile, args.outfile, device=args.device, check_crc=args.check_crc)
+    seconds = decode_wav(args.infile, args.outfile, device=args.device, check_crc=args.check_crc,
+                         spec_wasted_bits=args.spec_wasted_bits)
     print(f"Decoding completed in {seconds:.6g} seconds")
 
 
@@ -139,7 +148,7 @@ def cmd_encode(args) -> None:
     with args.outfile.open("wb") as f:
         for bs in encode_wav(args.infile, parameters, quirk=not args.correct_reader, device=args.device,
                              devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback,
-                             stereo=args.stereo, lpc_sign=args.lpc_sign):
+                             stereo=args.stereo, lpc_sign=args.lpc_sign, wasted=args.wasted_bits):
             f.write(bs)
     print(f"Encoding completed in {timer() - t0:.6g} seconds")
 

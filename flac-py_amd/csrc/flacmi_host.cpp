@@ -167,6 +167,7 @@ struct flacmi_ctx {
     uint16_t* d_crc = nullptr;  /* CRC-16 slice tables [4][256] + power tables [28][512] */
     DevBuf scan, h_offsets, h_status, h_frames, dec, slow;
     DevBuf h_subkind;           /* flacmi_encode_host's sub_kind array (FLACMI_FRAME_FALLBACK) */
+    DevBuf h_wasted;            /* flacmi_encode_host's wasted array (FLACMI_FRAME_WASTED) */
     DevBuf h_side, h_choice;    /* flacmi_encode_host's side rows and per-frame choice (FLACMI_STEREO_BEST) */
     DevBuf idx, sd_data, sd_table, sd_meta, sd_rows, sd_pcm; /* frame index workspace; flacmi_decode_stream_host's buffers */
     DevBuf si_frames, si_subs, si_parts; /* flacmi_info_stream_host's candidate records */
@@ -318,7 +319,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     for (auto& kv : ctx->chunk_weights) (void)hipFree(kv.second);
     for (DevBuf* b : {&ctx->bound, &ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->si_frames, &ctx->si_subs, &ctx->si_parts, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
-                      &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice})
+                      &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice, &ctx->h_wasted})
         if (b->p) (void)hipFree(b->p);
     if (ctx->d_log2thr) (void)hipFree(ctx->d_log2thr);
     if (ctx->d_sintab) (void)hipFree(ctx->d_sintab);
@@ -814,8 +815,10 @@ static int validate_frames(const flacmi_batch* b, const flacmi_frame_params* fp,
     if (fp->sample_size < 1 || fp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 1..32");
     if (fp->qlp_precision < 5 || fp->qlp_precision > 31) return fail(FLACMI_E_INVALID, "qlp_precision must be 5..31");
     if (fp->first_frame < 0) return fail(FLACMI_E_INVALID, "first_frame must be >= 0");
-    if (fp->reserved0 & ~FLACMI_FRAME_FALLBACK)
+    if (fp->reserved0 & ~(FLACMI_FRAME_FALLBACK | FLACMI_FRAME_WASTED))
         return fail(FLACMI_E_INVALID, "unknown frame flag bits %#x (reserved0)", (unsigned)fp->reserved0);
+    if ((fp->reserved0 & FLACMI_FRAME_WASTED) && fp->reserved[1] != FLACMI_STEREO_OFF)
+        return fail(FLACMI_E_INVALID, "FLACMI_FRAME_WASTED does not combine with the stereo mode (reserved[1])");
     if (fp->reserved[1] != FLACMI_STEREO_OFF && fp->reserved[1] != FLACMI_STEREO_BEST)
         return fail(FLACMI_E_INVALID, "unknown stereo mode %lld (reserved[1])", (long long)fp->reserved[1]);
     if (fp->reserved[1] == FLACMI_STEREO_BEST && (fp->channels != 2 || fp->sample_size > 31))
@@ -935,6 +938,35 @@ static int stereo_args(const flacmi_frame_params* fp, const flacmi_batch& db, De
     return 0;
 }
 
+/* ---- wasted-bits mode (FLACMI_FRAME_WASTED) at the host entry points ----------------------
+ * The host entry points own their device copy of the rows: k_wasted_rows shifts it in place, once
+ * per copy (a second run on shifted rows would find w = 0 and lose the shift), before the analysis,
+ * which then sees the units x >> w; the wasted array is the context's or the pipeline slot's. */
+static bool wasted_on(const flacmi_frame_params* fp) { return (fp->reserved0 & FLACMI_FRAME_WASTED) != 0; }
+static int no_wasted(const flacmi_frame_params* fp) {
+    if (wasted_on(fp))
+        return fail(FLACMI_E_INVALID, "the frame flag FLACMI_FRAME_WASTED (reserved0) is honoured by flacmi_encode_host and "
+                                      "flacmi_encode_pipeline only");
+    return 0;
+}
+static int wasted_shift(const flacmi_frame_params* fp, const flacmi_batch& db, DevBuf& buf, hipStream_t s) {
+    if (!wasted_on(fp)) return 0;
+    /* the kernel runs ahead of the analysis' own validation of the batch */
+    if ((db.sample_bytes != 2 && db.sample_bytes != 4) || db.sample_bits < 1 || db.sample_bits > 8 * db.sample_bytes)
+        return fail(FLACMI_E_INVALID, "sample_bytes must be 2 or 4 and sample_bits fit them");
+    if (db.n_tail_units > 0 && (db.tail_len < 1 || db.tail_len > db.block_len))
+        return fail(FLACMI_E_INVALID, "tail_len out of range");
+    if (int rc = ensure_buf(buf, sizeof(int32_t) * (size_t)db.n_units)) return rc;
+    const int bits = db.sample_bits < fp->sample_size ? db.sample_bits : fp->sample_size;
+    HIP_TRY(launch_wasted_rows(db.samples, db.sample_bytes, db.unit_stride, db.n_units, db.block_len,
+                               db.n_tail_units ? db.tail_len : db.block_len, db.n_tail_units, bits,
+                               const_cast<void*>(db.samples), db.unit_stride, (int32_t*)buf.p, s));
+    return 0;
+}
+static void wasted_args(const flacmi_frame_params* fp, DevBuf& buf, FrameArgs& a) {
+    if (wasted_on(fp)) a.wasted = (const int32_t*)buf.p;
+}
+
 /* the k_pack32 -> k_pack hand-off list (count word + one index per frame) */
 static int pack_lists(flacmi_ctx* ctx, FrameArgs& a) {
     if (int rc = ensure_buf(ctx->slow, sizeof(int64_t) * (size_t)(a.n_frames + 2))) return rc;
@@ -960,6 +992,7 @@ int flacmi_frame_sizes_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
     int64_t nf = 0;
     if (int rc = validate_frames(batch, fp, &nf)) return rc;
     if (int rc = no_stereo(fp)) return rc;
+    if (int rc = no_wasted(fp)) return rc;
     if (!meta || !rice_params || !frame_offsets || !frame_status) return fail(FLACMI_E_INVALID, "null buffer");
     if (int rc = set_device(ctx)) return rc;
     if (nf == 0) {
@@ -980,6 +1013,7 @@ int flacmi_pack_frames_device(flacmi_ctx* ctx, const flacmi_batch* batch, const 
     int64_t nf = 0;
     if (int rc = validate_frames(batch, fp, &nf)) return rc;
     if (int rc = no_stereo(fp)) return rc;
+    if (int rc = no_wasted(fp)) return rc;
     if (!meta || !rice_params || !residual || !frame_offsets || !frame_status || (!out && out_capacity > 0))
         return fail(FLACMI_E_INVALID, "null buffer");
     if (residual_bytes != 4 && residual_bytes != 8) return fail(FLACMI_E_INVALID, "residual_bytes must be 4 or 8");
@@ -1026,6 +1060,34 @@ int flacmi_stereo_rows_device(flacmi_ctx* ctx, const flacmi_batch* lr, void* mid
     return 0;
 }
 
+int flacmi_wasted_rows_device(flacmi_ctx* ctx, const flacmi_batch* in, void* out_rows, int64_t out_stride,
+                              int32_t* wasted, void* stream) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
+    if (!in || !out_rows || !wasted) return fail(FLACMI_E_INVALID, "null argument");
+    if (in->sample_bytes != 2 && in->sample_bytes != 4) return fail(FLACMI_E_INVALID, "sample_bytes must be 2 or 4");
+    if (in->sample_bits < 1 || in->sample_bits > 8 * in->sample_bytes)
+        return fail(FLACMI_E_INVALID, "sample_bits out of range for the row type");
+    if (in->n_units < 0 || in->n_tail_units < 0 || in->n_tail_units > in->n_units)
+        return fail(FLACMI_E_INVALID, "n_units / n_tail_units out of range");
+    if (in->block_len < 1 || in->block_len > FLACMI_MAX_BLOCK) return fail(FLACMI_E_INVALID, "block_len out of range");
+    if (in->n_tail_units > 0 && (in->tail_len < 1 || in->tail_len > in->block_len))
+        return fail(FLACMI_E_INVALID, "tail_len out of range");
+    if (in->n_units == 0) return 0;
+    if (!in->samples) return fail(FLACMI_E_INVALID, "null argument");
+    if (in->unit_stride < in->block_len || out_stride < in->block_len)
+        return fail(FLACMI_E_INVALID, "a row pitch is below block_len");
+    if ((in->unit_stride * in->sample_bytes) % 16 != 0 || (out_stride * in->sample_bytes) % 16 != 0 ||
+        ((uintptr_t)in->samples | (uintptr_t)out_rows) % 16 != 0 || (uintptr_t)wasted % 4 != 0)
+        return fail(FLACMI_E_INVALID, "rows must be 16-byte aligned and every pitch a multiple of 16 bytes");
+    if (out_rows == in->samples && out_stride != in->unit_stride)
+        return fail(FLACMI_E_INVALID, "in place the output pitch is the input pitch");
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(launch_wasted_rows(in->samples, in->sample_bytes, in->unit_stride, in->n_units, in->block_len,
+                               in->tail_len, in->n_tail_units, in->sample_bits, out_rows, out_stride, wasted,
+                               (hipStream_t)stream));
+    return 0;
+}
+
 int flacmi_decode_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
                                 const int64_t* frame_offsets, int64_t n_frames,
                                 const flacmi_decode_params* dp, const flacmi_batch* expect,
@@ -1033,6 +1095,13 @@ int flacmi_decode_frames_device(flacmi_ctx* ctx, const uint8_t* stream_data, int
                                 int64_t* frame_mismatch, void* stream) {
     return flacmi_decode_frames_end_device(ctx, stream_data, stream_bytes, frame_offsets, n_frames, dp, expect,
                                            samples_out, out_stride, frame_status, frame_mismatch, nullptr, stream);
+}
+
+/* flacmi_decode_params.reserved0: enum flacmi_decode_flags bits */
+static int decode_flags_ok(const flacmi_decode_params* dp) {
+    if (dp->reserved0 & ~FLACMI_DECODE_WASTED_SPEC)
+        return fail(FLACMI_E_INVALID, "unknown decode flag bits %#x (reserved0)", (unsigned)dp->reserved0);
+    return 0;
 }
 
 static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
@@ -1063,6 +1132,7 @@ static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64
     if (((uintptr_t)stream_data & 3) != 0) return fail(FLACMI_E_INVALID, "stream_data must be 4-byte aligned");
     if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
     if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
     if (samples_out && (out_stride < 1 || (out_stride & 3) != 0 || ((uintptr_t)samples_out & 15) != 0))
         return fail(FLACMI_E_INVALID, "samples_out rows must be 16-byte aligned (out_stride a multiple of 4)");
     if (expect) {
@@ -1087,6 +1157,7 @@ static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64
     a.sample_size = dp->sample_size;
     a.first_frame = dp->first_frame;
     a.check_crc = dp->check_crc;
+    a.wasted_spec = (dp->reserved0 & FLACMI_DECODE_WASTED_SPEC) != 0;
     if (expect) {
         a.expect = expect->samples;
         a.expect_stride = expect->unit_stride;
@@ -1281,6 +1352,7 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
     if (pcm_capacity > 0 && !pcm) return fail(FLACMI_E_INVALID, "null pcm buffer");
     if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
     if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
     if (max_block_size < 0 || max_block_size > FLACMI_MAX_BLOCK + 1) return fail(FLACMI_E_INVALID, "max_block_size must be 0..65536");
     if (mode != FLACMI_PCM_PACKED && mode != FLACMI_PCM_RAW32) return fail(FLACMI_E_INVALID, "mode must be a flacmi_pcm_mode");
     if (mode == FLACMI_PCM_PACKED && (bytes_per_sample < 1 || bytes_per_sample > 4))
@@ -1522,6 +1594,7 @@ int flacmi_frame_info_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_
         return fail(FLACMI_E_INVALID, "frame_offsets, frame_info and subframe_info must be 8-byte aligned");
     if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
     if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
     if (int rc = set_device(ctx)) return rc;
     InfoArgs a{};
     a.words = reinterpret_cast<const uint32_t*>(stream_data);
@@ -1536,6 +1609,7 @@ int flacmi_frame_info_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_
     a.parts = part_stride > 0 ? part_params : nullptr;
     a.part_stride = (int32_t)part_stride;
     a.crc_slice = ctx->d_crc;
+    a.wasted_spec = (dp->reserved0 & FLACMI_DECODE_WASTED_SPEC) != 0;
     HIP_TRY(launch_frame_info(a, knob(kKnobInfoGrid), (hipStream_t)stream));
     return 0;
 }
@@ -1552,6 +1626,7 @@ int flacmi_info_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes,
     if (part_stride > 0 && frame_capacity > 0 && !part_params) return fail(FLACMI_E_INVALID, "null part_params");
     if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
     if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
     memset(res, 0, sizeof(*res));
     res->consumed = first_byte;
     if (bytes == first_byte) return 0;
@@ -1715,6 +1790,7 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
     HIP_TRY(hipMemcpy2DAsync(ctx->h_samples.p, sstride * batch->sample_bytes, batch->samples,
                              batch->unit_stride * batch->sample_bytes, batch->block_len * batch->sample_bytes, nu,
                              hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = wasted_shift(fp, db, ctx->h_wasted, ctx->stream)) return rc; /* once, before the redo loop */
     for (int rbytes = 4;; rbytes = 8) {
         const int64_t rstride = ((batch->block_len * rbytes + 15) / 16) * 16 / rbytes;
         if (int rc = ensure_buf(ctx->h_residual, nou * rstride * rbytes)) return rc;
@@ -1734,6 +1810,7 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
         FrameArgs a = frame_args(ctx, &db, fp, o.meta, o.rice_params, pstride, nf);
         if (int rc = stereo_args(fp, db, ctx->h_side, ctx->h_choice, a)) return rc;
         if (int rc = own_sub_kind(fp, ctx->h_subkind, a)) return rc;
+        wasted_args(fp, ctx->h_wasted, a);
         if (int rc = frame_sizes_impl(ctx, a, (int64_t*)ctx->h_offsets.p, (int32_t*)ctx->h_status.p, ctx->stream))
             return rc;
         HIP_TRY(hipMemcpyAsync(frame_offsets, ctx->h_offsets.p, sizeof(int64_t) * (nf + 1), hipMemcpyDeviceToHost,
@@ -1782,6 +1859,7 @@ constexpr int kEncSlots = 4; /* with 3 the host waited for the D2H of sub-batch 
 struct EncSlot {
     DevBuf samples, meta, params, residual, offsets, status, frames;
     DevBuf subkind;             /* sub_kind of the sub-batch's units (FLACMI_FRAME_FALLBACK) */
+    DevBuf wasted;              /* wasted bits of the sub-batch's units (FLACMI_FRAME_WASTED) */
     DevBuf side, choice;        /* side rows and per-frame choice of the sub-batch (FLACMI_STEREO_BEST) */
     int64_t* h_off = nullptr;   /* pinned, mapped: frame offsets of the sub-batch */
     int32_t* h_st = nullptr;    /* pinned, mapped: frame status */
@@ -1812,7 +1890,7 @@ static void enc_free(EncState* es) {
         if (st) (void)hipStreamSynchronize(st);
     for (auto& sl : es->slot) {
         for (DevBuf* d : {&sl.samples, &sl.meta, &sl.params, &sl.residual, &sl.offsets, &sl.status, &sl.frames,
-                          &sl.subkind, &sl.side, &sl.choice})
+                          &sl.subkind, &sl.side, &sl.choice, &sl.wasted})
             if (d->p) (void)hipFree(d->p);
         if (sl.h_off) (void)hipHostFree(sl.h_off);
         if (sl.h_st) (void)hipHostFree(sl.h_st);
@@ -1900,6 +1978,8 @@ static int enc_front(flacmi_ctx* ctx, EncSlot& sl, const flacmi_batch* whole, co
     flacmi_batch db = b;
     db.samples = sl.samples.p;
     db.unit_stride = sstride;
+    /* on the rows this call has just copied (a redo with 8-byte residual rows copies them again) */
+    if (int rc = wasted_shift(fp, db, sl.wasted, cs)) return rc;
     flacmi_outputs o{};
     o.meta = (flacmi_unit_meta*)sl.meta.p;
     o.rice_params = (int32_t*)sl.params.p;
@@ -1921,6 +2001,7 @@ static int enc_front(flacmi_ctx* ctx, EncSlot& sl, const flacmi_batch* whole, co
     FrameArgs a = frame_args(ctx, &db, &f, o.meta, o.rice_params, pstride, sl.nf);
     if (int rc = stereo_args(fp, db, sl.side, sl.choice, a)) return rc;
     if (int rc = own_sub_kind(fp, sl.subkind, a)) return rc;
+    wasted_args(fp, sl.wasted, a);
     if (int rc = frame_sizes_impl(ctx, a, (int64_t*)sl.offsets.p, (int32_t*)sl.status.p, cs)) return rc;
     HIP_TRY(hipEventRecord(sl.e[3], cs));
     HIP_TRY(launch_export((const int64_t*)sl.offsets.p, (const int32_t*)sl.status.p, sl.nf, sl.d_off, sl.d_st, cs));
@@ -2056,6 +2137,7 @@ extern "C" int flacmi_encode_pipeline(flacmi_ctx* ctx, const flacmi_batch* batch
                                      pstride, sl.nf);
             if (int r = stereo_args(fp, db, sl.side, sl.choice, a)) return r; /* what enc_front's kernels wrote */
             if (int r = own_sub_kind(fp, sl.subkind, a)) return r; /* the array enc_front's k_sub_kinds wrote */
+            wasted_args(fp, sl.wasted, a); /* and the one its k_wasted_rows wrote */
             a.residual = sl.residual.p;
             a.residual_bytes = sl.rbytes;
             a.residual_stride = rstride;

@@ -140,6 +140,8 @@ struct FrameArgs {
     int64_t mid_stride;
     const int32_t* side;       /* side rows [n_frames], sample_size + 1 bits in int32 */
     int64_t side_stride;
+    const int32_t* wasted;     /* FLACMI_FRAME_WASTED: [n_units] wasted bits of the units, whose rows are already
+                                  shifted right by them (k_wasted_rows); NULL: the mode is off.  Not with choice */
 };
 
 /* Decoder verifier (k_decode.hip): frame f = bytes [offsets[f], offsets[f+1]) of words. */
@@ -171,6 +173,7 @@ struct DecodeArgs {
     int32_t lpc_pass;                 /* k_decode_fx's LPC pass runs (knob FLACMI_DECODE_LPC=0: off) */
     int64_t* frame_end;               /* optional [n_frames]: the byte after the frame's footer where the
                                          frame raised no reference exception, else -1 */
+    int32_t wasted_spec;             /* FLACMI_DECODE_WASTED_SPEC: wasted bits = zeros + 1, shifted back in */
 };
 
 /* Frame index (k_index.hip): candidate frame starts of a byte stream, in stream order.  A tile
@@ -241,6 +244,7 @@ struct InfoArgs {
     uint8_t* parts;              /* [n_frames][channels][part_stride], or nullptr */
     int32_t part_stride;
     const uint16_t* crc_slice;   /* [4][256] CRC-16 slice-by-4 tables */
+    int32_t wasted_spec;         /* FLACMI_DECODE_WASTED_SPEC: wasted_bits = zeros + 1, sample_bits accordingly */
 };
 
 /* PCM writer (k_index.hip, k_pcm) */
@@ -295,6 +299,14 @@ hipError_t launch_stats(const flacmi_unit_meta* meta, int64_t n_units, int32_t b
 hipError_t launch_stereo_rows(const void* lr, int32_t sample_bytes, int64_t lr_stride, int64_t n_frames,
                               int32_t block_len, int32_t tail_len, int32_t has_tail, void* mid, int64_t mid_stride,
                               int32_t* side, int64_t side_stride, hipStream_t s);
+/* Wasted bits (k_wasted.hip): wasted[u] = 0 for an all-zero unit, else min(ctz(OR of its samples),
+ * sample_bits - 1), and out row u = in row u >> wasted[u]; len samples a row (tail_len for the last
+ * n_tail_units units), nothing at or past a unit's length is read or written.  out may be in (with
+ * the same pitch): units with wasted[u] == 0 are then not stored.  Every row 16-byte aligned,
+ * every pitch a multiple of 16 bytes. */
+hipError_t launch_wasted_rows(const void* in, int32_t sample_bytes, int64_t in_stride, int64_t n_units,
+                              int32_t block_len, int32_t tail_len, int64_t n_tail_units, int32_t sample_bits,
+                              void* out, int64_t out_stride, int32_t* wasted, hipStream_t s);
 /* a.choice[f] from the four candidates' sizes (after k_sub_kinds in the fallback mode) */
 hipError_t launch_stereo_choose(const FrameArgs& a, hipStream_t s);
 

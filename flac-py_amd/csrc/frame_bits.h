@@ -10,10 +10,12 @@ __device__ __forceinline__ int unit_len(const FrameArgs& a, int64_t u) {
     return u >= a.n_units - a.n_tail_units ? a.tail_len : a.block_len;
 }
 
-/* Bits of the subframe up to the first partition (encoder.py:553-627, :766-767). */
-__device__ __forceinline__ uint32_t sub_prefix_bits(const flacmi_unit_meta& m, int ss, int q) {
+/* Bits of the subframe up to the first partition (encoder.py:553-627, :766-767).  ss: the width
+ * the unit's samples are written at; w: its wasted bits (FLACMI_FRAME_WASTED: the header is
+ * 0 tttttt 1, w - 1 zeros and a one, 8 + w bits, and ss is the stream's sample size less w). */
+__device__ __forceinline__ uint32_t sub_prefix_bits(const flacmi_unit_meta& m, int ss, int q, int w = 0) {
     const bool lpc = m.kind == FLACMI_KIND_LPC;
-    return 8u + (uint32_t)m.order * (uint32_t)ss + (lpc ? 9u + (uint32_t)m.ncoefs * (uint32_t)q : 0u) + 6u;
+    return 8u + (uint32_t)w + (uint32_t)m.order * (uint32_t)ss + (lpc ? 9u + (uint32_t)m.ncoefs * (uint32_t)q : 0u) + 6u;
 }
 
 /* Written residual bits (partition parameters + Rice codes) from the reference's estimate
@@ -34,10 +36,18 @@ __device__ __forceinline__ int sub_kind_of(const FrameArgs& a, int64_t u) {
     else return 0;
 }
 
-/* Bits of a CONSTANT / VERBATIM subframe (encoder.py:553-578): the header byte and one or n
- * samples of ss bits. */
-__device__ __forceinline__ uint32_t sub_raw_bits(int kind, int n, int ss) {
-    return 8u + (kind == FLACMI_SUB_CONSTANT ? 1u : (uint32_t)n) * (uint32_t)ss;
+/* Bits of a CONSTANT / VERBATIM subframe (encoder.py:553-578): the header byte (and the w bits
+ * of the wasted code) and one or n samples of ss bits. */
+__device__ __forceinline__ uint32_t sub_raw_bits(int kind, int n, int ss, int w = 0) {
+    return 8u + (uint32_t)w + (kind == FLACMI_SUB_CONSTANT ? 1u : (uint32_t)n) * (uint32_t)ss;
+}
+
+/* WB: the build of a kernel for the wasted-bits mode (a.wasted set; never together with ST); the
+ * other builds never look at the array, so they are the code they were before the mode existed. */
+template <bool WB>
+__device__ __forceinline__ int unit_wasted(const FrameArgs& a, int64_t u) {
+    if constexpr (WB) return a.wasted[u];
+    else return 0;
 }
 
 /* ---- the stereo mode's units (FLACMI_STEREO_BEST, a.choice set) ------------------------
@@ -57,11 +67,11 @@ __device__ __forceinline__ int unit_len_of(const FrameArgs& a, int64_t u) {
     else return unit_len(a, u);
 }
 
-/* bits of a warm-up or raw sample of unit u */
+/* bits of a warm-up or raw sample of unit u; w: the unit's wasted bits (unit_wasted) */
 template <bool ST>
-__device__ __forceinline__ int unit_bits_of(const FrameArgs& a, int64_t u) {
+__device__ __forceinline__ int unit_bits_of(const FrameArgs& a, int64_t u, int w = 0) {
     if constexpr (ST) return a.sample_size + (u >= 3 * a.n_frames ? 1 : 0);
-    else return a.sample_size;
+    else return a.sample_size - w;
 }
 
 /* unit u's sample row and its element size in bytes */

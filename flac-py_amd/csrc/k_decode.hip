@@ -171,9 +171,14 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
                 ++wasted;
                 if (g.pos() > end_bit) break;
             }
+            if (a.wasted_spec) ++wasted; /* the format codes k as k - 1 zeros and a one */
         }
         const int w = ss + (dbit ? 1 : 0) - wasted; /* sample_size_ (decoder.py:276) */
         if (w <= 0) { pfail(DS_ESC_ZERO); break; }
+        /* FLACMI_DECODE_WASTED_SPEC: a restored sample leaves the ring shifted back (the prediction
+         * reads the ring as parsed); off: parsed, not applied (decode_subframe) */
+        const int wsh = a.wasted_spec ? wasted : 0;
+        auto rs = [&](int k) { return (int32_t)(uint32_t)((uint64_t)(uint32_t)ring[k][lane] << wsh); }; /* wsh <= 32 */
         const int order = t >= 32 ? (t & 31) + 1 : t >= 8 ? (t & 7) : 0;
         int64_t cval = 0;
         int shift = 0;
@@ -255,11 +260,11 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
                     if (cnt == 32) {
 #pragma unroll
                         for (int k = 0; k < 32; k += 4) {
-                            int4v v = {ring[k][lane], ring[k + 1][lane], ring[k + 2][lane], ring[k + 3][lane]};
+                            int4v v = {rs(k), rs(k + 1), rs(k + 2), rs(k + 3)};
                             *reinterpret_cast<int4v*>(orow + c0 + k) = v;
                         }
                     } else {
-                        for (int k = 0; k < cnt; ++k) orow[c0 + k] = ring[k][lane];
+                        for (int k = 0; k < cnt; ++k) orow[c0 + k] = rs(k);
                     }
                 }
                 if (cmp) {
@@ -272,8 +277,8 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
                                 const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                                 for (int h = 0; h < 4; ++h) {
-                                    bad += ring[8 * g2 + 2 * h][lane] != ((int32_t)(w[h] << 16) >> 16);
-                                    bad += ring[8 * g2 + 2 * h + 1][lane] != ((int32_t)w[h] >> 16);
+                                    bad += rs(8 * g2 + 2 * h) != ((int32_t)(w[h] << 16) >> 16);
+                                    bad += rs(8 * g2 + 2 * h + 1) != ((int32_t)w[h] >> 16);
                                 }
                             }
                         } else {
@@ -282,11 +287,11 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
                             for (int g2 = 0; g2 < 8; ++g2) {
                                 const int4v v = e4[g2];
 #pragma unroll
-                                for (int h = 0; h < 4; ++h) bad += ring[4 * g2 + h][lane] != v[h];
+                                for (int h = 0; h < 4; ++h) bad += rs(4 * g2 + h) != v[h];
                             }
                         }
                     } else {
-                        for (int k = 0; k < cnt; ++k) bad += ring[k][lane] != expect_at(a, u, c0 + k);
+                        for (int k = 0; k < cnt; ++k) bad += rs(k) != expect_at(a, u, c0 + k);
                     }
                 }
             }

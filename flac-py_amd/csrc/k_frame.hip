@@ -143,14 +143,16 @@ __device__ int frame_header_st(int64_t fno, int bs, int chan, uint8_t* h) {
  * or the LPC path has raised before), so only units with a nonzero status are scanned; a unit
  * escaped for its size or for the precision assertion is VERBATIM without reading its row.
  * ==================================================================================== */
-template <bool ST> /* ST: over the stereo mode's 4 n_frames candidate units, the side units one bit wider */
+template <bool ST, bool WB = false> /* ST: over the stereo mode's 4 n_frames candidate units, the side units one bit
+                                       wider; WB: the wasted-bits mode, a unit at its own width and header */
 __device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
     const int lane = threadIdx.x & 63;
     const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= (ST ? 4 * a.n_frames : a.n_units)) return;
     const flacmi_unit_meta& m = a.meta[u];
     const int n = unit_len_of<ST>(a, u);
-    const int ss = unit_bits_of<ST>(a, u);
+    const int wz = unit_wasted<WB>(a, u);
+    const int ss = unit_bits_of<ST>(a, u, wz);
     const int st = m.status;
     bool esc;
     if (st != 0) {
@@ -165,7 +167,7 @@ __device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
             for (int k = lane; k < m.n_parts; k += 64) cnt += rp[k] > 14 ? 1 : 0;
             for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
         }
-        esc = (int64_t)sub_prefix_bits(m, ss, a.q) + sub_residual_bits(m, cnt) > 8 + (int64_t)n * ss;
+        esc = (int64_t)sub_prefix_bits(m, ss, a.q, wz) + sub_residual_bits(m, cnt) > 8 + wz + (int64_t)n * ss;
     }
     if (!esc || st == 0) {
         if (lane == 0) a.sub_kind[u] = esc ? FLACMI_SUB_VERBATIM : FLACMI_SUB_ANALYSED;
@@ -197,11 +199,13 @@ __device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
 }
 __global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) { sub_kinds<false>(a); }
 __global__ __launch_bounds__(256) void k_sub_kinds_st(FrameArgs a) { sub_kinds<true>(a); }
+__global__ __launch_bounds__(256) void k_sub_kinds_wb(FrameArgs a) { sub_kinds<false, true>(a); }
 
 /* ====================================================================================
  * k_frame_sizes: one wave per frame
  * ==================================================================================== */
-template <bool FB, bool ST = false> /* ST: the stereo mode's build (the frame's two units and code from a.choice) */
+template <bool FB, bool ST = false, bool WB = false> /* ST: the stereo mode's build (the frame's two units and code
+                                                        from a.choice); WB: the wasted-bits mode's */
 __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
     const int lane = threadIdx.x & 63;
     const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -218,10 +222,11 @@ __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
     for (int c = 0; c < a.channels && st == 0; ++c) {
         int64_t u = u0 + c;
         if constexpr (ST) u = a.choice[f].unit[c];
-        const int ss = unit_bits_of<ST>(a, u);
+        const int wz = unit_wasted<WB>(a, u);
+        const int ss = unit_bits_of<ST>(a, u, wz);
         const flacmi_unit_meta& m = a.meta[u];
         if (const int kind = sub_kind_of<FB>(a, u)) { /* escaped: no status, no meta */
-            bits += sub_raw_bits(kind, bs, ss);
+            bits += sub_raw_bits(kind, bs, ss, wz);
             continue;
         }
         if (m.status != 0) {
@@ -238,7 +243,7 @@ __device__ __forceinline__ void frame_sizes(const FrameArgs& a) {
             for (int k = lane; k < m.n_parts; k += 64) cnt += rp[k] > 14 ? 1 : 0;
             for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
         }
-        bits += (int64_t)sub_prefix_bits(m, ss, a.q) + sub_residual_bits(m, cnt);
+        bits += (int64_t)sub_prefix_bits(m, ss, a.q, wz) + sub_residual_bits(m, cnt);
     }
     int64_t bytes = 0;
     if (st == 0) {
@@ -258,6 +263,8 @@ __global__ __launch_bounds__(256) void k_frame_sizes(FrameArgs a) { frame_sizes<
 __global__ __launch_bounds__(256) void k_frame_sizes_fb(FrameArgs a) { frame_sizes<true>(a); }
 __global__ __launch_bounds__(256) void k_frame_sizes_st(FrameArgs a) { frame_sizes<false, true>(a); }
 __global__ __launch_bounds__(256) void k_frame_sizes_st_fb(FrameArgs a) { frame_sizes<true, true>(a); }
+__global__ __launch_bounds__(256) void k_frame_sizes_wb(FrameArgs a) { frame_sizes<false, false, true>(a); }
+__global__ __launch_bounds__(256) void k_frame_sizes_wb_fb(FrameArgs a) { frame_sizes<true, false, true>(a); }
 
 /* ---- exclusive scan of frame sizes (in place on offsets[1..n]) ---------------------- */
 constexpr int kScanItems = 8;
@@ -435,7 +442,7 @@ __device__ __forceinline__ bool pack32_frame_ok(const FrameArgs& a, int64_t f, i
 
 /* ST: the stereo mode's build (a.choice: the frame's channel code and its two candidate units,
  * the side unit one bit wider) */
-template <typename ZT, bool FB, bool ST = false>
+template <typename ZT, bool FB, bool ST = false, bool WB = false>
 __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) {
     __shared__ uint32_t win[kWinWords];
     __shared__ uint16_t ct[4 * 256];
@@ -483,9 +490,10 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
             const flacmi_unit_meta& m = a.meta[u];
             sub_start[c] = s;
             const int kind = sub_kind_of<FB>(a, u);
-            const int w = unit_bits_of<ST>(a, u);
-            s += kind ? sub_raw_bits(kind, unit_len_of<ST>(a, u), w)
-                      : sub_prefix_bits(m, w, a.q) + (uint32_t)sub_residual_bits(m, cnt14[c]);
+            const int wz = unit_wasted<WB>(a, u);
+            const int w = unit_bits_of<ST>(a, u, wz);
+            s += kind ? sub_raw_bits(kind, unit_len_of<ST>(a, u), w, wz)
+                      : sub_prefix_bits(m, w, a.q, wz) + (uint32_t)sub_residual_bits(m, cnt14[c]);
         }
         sub_start[C] = s;
     }
@@ -512,8 +520,13 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
         const int64_t u = unit_of(c);
         const flacmi_unit_meta& m = a.meta[u];
         const int n = unit_len_of<ST>(a, u);
-        const int ss = unit_bits_of<ST>(a, u);
+        /* the wasted-bits mode: the header byte's last bit set, then wz - 1 zeros and a one, and
+         * everything behind the header wz bits later at ss = sample_size - wz bits a sample */
+        const int wz = unit_wasted<WB>(a, u);
+        const int ss = unit_bits_of<ST>(a, u, wz);
         const uint32_t s0 = sub_start[c];
+        const uint32_t h8 = 8u + (uint32_t)wz; /* the subframe header's bits */
+        const uint64_t wflag = wz ? 1 : 0;
         if (const int kind = sub_kind_of<FB>(a, u)) {
             /* CONSTANT / VERBATIM (encoder.py:559-578): the header byte, then 1 or n samples as
              * ss-bit fields, 8 per thread a tile (a tile is at most 64 Kbit, half a window).  No
@@ -523,11 +536,14 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
             const uint64_t smask = (1ull << ss) - 1;
             for (int t0 = 0; t0 < cnt; t0 += 8 * NT) {
                 const int t1 = t0 + 8 * NT < cnt ? t0 + 8 * NT : cnt;
-                segment(s0 + 8u + (uint32_t)t1 * ss, [&]() {
-                    if (t0 == 0 && tid == 0) win_or(win, wb, s0, (uint64_t)(kind == FLACMI_SUB_CONSTANT ? 0 : 2), 8);
+                segment(s0 + h8 + (uint32_t)t1 * ss, [&]() {
+                    if (t0 == 0 && tid == 0) {
+                        win_or(win, wb, s0, (uint64_t)(kind == FLACMI_SUB_CONSTANT ? 0 : 2) | wflag, 8);
+                        if (wz) win_or(win, wb, s0 + 8u, 1, wz);
+                    }
                     for (int i = t0 + 8 * tid; i < t1 && i < t0 + 8 * tid + 8; ++i) {
                         const int64_t x = unit_sample<ST>(a, u, i);
-                        win_or(win, wb, s0 + 8u + (uint32_t)i * ss, (uint64_t)x & smask, ss);
+                        win_or(win, wb, s0 + h8 + (uint32_t)i * ss, (uint64_t)x & smask, ss);
                     }
                 });
             }
@@ -535,26 +551,27 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
         }
         const int order = m.order, ncoefs = m.ncoefs, method = m.coding_method;
         const bool lpc = m.kind == FLACMI_KIND_LPC;
-        const uint32_t pre = sub_prefix_bits(m, ss, q);
+        const uint32_t pre = sub_prefix_bits(m, ss, q, wz);
         /* subframe header, warm-up, LPC fields, residual header: field t per thread */
         const int nfields = 1 + order + (lpc ? 2 + ncoefs : 0) + 2;
         segment(s0 + pre, [&]() {
+            if (wz && tid == NT - 1) win_or(win, wb, s0 + 8u, 1, wz);
             for (int t = tid; t < nfields; t += NT) {
                 uint32_t pos;
                 uint64_t v;
                 int w;
                 if (t == 0) {
                     pos = s0;
-                    v = lpc ? (uint64_t)((0x20 | (order - 1)) << 1) : (uint64_t)((0x08 | order) << 1);
+                    v = (lpc ? (uint64_t)((0x20 | (order - 1)) << 1) : (uint64_t)((0x08 | order) << 1)) | wflag;
                     w = 8;
                 } else if (t <= order) {
                     const int j = t - 1;
                     const int64_t x = unit_sample<ST>(a, u, j);
-                    pos = s0 + 8 + (uint32_t)j * ss;
+                    pos = s0 + h8 + (uint32_t)j * ss;
                     v = (uint64_t)x & (ss == 64 ? ~0ull : ((1ull << ss) - 1));
                     w = ss;
                 } else {
-                    const uint32_t b = s0 + 8 + (uint32_t)order * ss;
+                    const uint32_t b = s0 + h8 + (uint32_t)order * ss;
                     const int t2 = t - 1 - order;
                     if (lpc && t2 == 0) {
                         pos = b;
@@ -738,7 +755,7 @@ __device__ __forceinline__ void pack_frame(const FrameArgs& a, const int64_t f) 
 
 /* General frame writer: every frame (pack_split = 0), or, after k_pack32, the frames it
  * listed (grid-stride over the list; an empty list costs one short launch). */
-template <typename ZT, bool FB, bool ST = false>
+template <typename ZT, bool FB, bool ST = false, bool WB = false>
 __device__ __forceinline__ void pack_frames(const FrameArgs& a) {
     if (a.offsets[a.n_frames] > a.capacity) {
         if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -747,7 +764,7 @@ __device__ __forceinline__ void pack_frames(const FrameArgs& a) {
     }
     const int64_t cnt = a.pack_split ? (int64_t)*a.slow_count : (int64_t)blockIdx.x + 1;
     for (int64_t idx = blockIdx.x; idx < cnt; idx += gridDim.x) { /* one call site: inlined once */
-        pack_frame<ZT, FB, ST>(a, a.pack_split ? a.slow_list[idx] : idx);
+        pack_frame<ZT, FB, ST, WB>(a, a.pack_split ? a.slow_list[idx] : idx);
         __syncthreads(); /* LDS reuse by the next frame */
     }
 }
@@ -761,6 +778,12 @@ template <typename ZT>
 __global__ __launch_bounds__(kPackThreads) void k_pack_st(FrameArgs a) { pack_frames<ZT, false, true>(a); }
 template <typename ZT>
 __global__ __launch_bounds__(kPackThreads) void k_pack_st_fb(FrameArgs a) { pack_frames<ZT, true, true>(a); }
+/* the wasted-bits mode's builds (every frame of such a batch goes through them: the fast writers
+ * know no variable-length subframe header) */
+template <typename ZT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_wb(FrameArgs a) { pack_frames<ZT, false, false, true>(a); }
+template <typename ZT>
+__global__ __launch_bounds__(kPackThreads) void k_pack_wb_fb(FrameArgs a) { pack_frames<ZT, true, false, true>(a); }
 
 /* ====================================================================================
  * k_pack32: the frame writer for frames that fit one LDS window (32-bit residuals).
@@ -1552,6 +1575,15 @@ hipError_t launch_frame_sizes(const FrameArgs& a, int64_t* bsum, hipStream_t s) 
         if (e != hipSuccess) return e;
         if (a.sub_kind) hipLaunchKernelGGL(k_frame_sizes_st_fb, frames4, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_frame_sizes_st, frames4, dim3(256), 0, s, a);
+    } else if (a.wasted) { /* wasted-bits mode: the units at their own widths and headers */
+        if (a.sub_kind) {
+            hipLaunchKernelGGL(k_sub_kinds_wb, dim3((unsigned)((a.n_units + 3) / 4)), dim3(256), 0, s, a);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_frame_sizes_wb_fb, frames4, dim3(256), 0, s, a);
+        } else {
+            hipLaunchKernelGGL(k_frame_sizes_wb, frames4, dim3(256), 0, s, a);
+        }
     } else if (a.sub_kind) { /* fallback mode: one more launch, on the stream between the analysis and the sizes */
         hipLaunchKernelGGL(k_sub_kinds, dim3((unsigned)((a.n_units + 3) / 4)), dim3(256), 0, s, a);
         hipError_t e = hipGetLastError();
@@ -1605,6 +1637,17 @@ hipError_t launch_pack(const FrameArgs& a, hipStream_t s) {
         } else {
             if (fb) hipLaunchKernelGGL(k_pack_st_fb<uint32_t>, g, t, 0, s, a);
             else hipLaunchKernelGGL(k_pack_st<uint32_t>, g, t, 0, s, a);
+        }
+        return hipGetLastError();
+    }
+    if (a.wasted) { /* wasted-bits mode: the general writer for every frame */
+        const dim3 g((unsigned)a.n_frames), t(nt);
+        if (a.residual_bytes == 8) {
+            if (fb) hipLaunchKernelGGL(k_pack_wb_fb<uint64_t>, g, t, 0, s, a);
+            else hipLaunchKernelGGL(k_pack_wb<uint64_t>, g, t, 0, s, a);
+        } else {
+            if (fb) hipLaunchKernelGGL(k_pack_wb_fb<uint32_t>, g, t, 0, s, a);
+            else hipLaunchKernelGGL(k_pack_wb<uint32_t>, g, t, 0, s, a);
         }
         return hipGetLastError();
     }

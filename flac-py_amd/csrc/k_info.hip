@@ -149,6 +149,7 @@ __device__ void frame_info(const InfoArgs& a, const int64_t f, const uint16_t* c
                     ++wasted;
                     if (g.pos() > end_bit) break;
                 }
+                if (a.wasted_spec) ++wasted; /* FLACMI_DECODE_WASTED_SPEC: k is coded as k - 1 zeros and a one */
             }
             const int w = ss + (dbit ? 1 : 0) - wasted; /* sample_size_ (decoder.py:273) */
             if (w <= 0) return err(DS_ESC_ZERO);

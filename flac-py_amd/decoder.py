@@ -87,7 +87,7 @@ def _analyzer(device: int):
 
 
 def _chunks(buffer, streaminfo: Streaminfo, raw: bool, chunk_bytes: int, device: int, check_crc: bool,
-            stats, pcm_buffer_bytes: int = 0) -> Iterator[bytes]:
+            stats, pcm_buffer_bytes: int = 0, spec_wasted_bits: bool = False) -> Iterator[bytes]:
     """Interleaved PCM of the frames at `buffer`'s position, one bytes object per call of
     flacmi_decode_stream_host; raises the stopping exception after the last good frame."""
     from ._lib import FlacmiError
@@ -115,7 +115,8 @@ def _chunks(buffer, streaminfo: Streaminfo, raw: bool, chunk_bytes: int, device:
         while True:
             try:
                 res = az.decode_stream(stage.ctypes.data, n, 0, channels, streaminfo.sample_size, check_crc,
-                                       streaminfo.max_block_size, final, pcm.ctypes.data, len(pcm), raw, B)
+                                       streaminfo.max_block_size, final, pcm.ctypes.data, len(pcm), raw, B,
+                                       spec_wasted_bits)
                 break
             except FlacmiError as e:
                 if e.code != abi.E_NOMEM or len(pcm) >= (1 << 33):
@@ -146,24 +147,29 @@ def _open(buffer_or_path):
 
 
 def decode(buffer, check_crc: bool = False, chunk_bytes: int = DEFAULT_CHUNK_BYTES, device: int = 0,
-           stats=None, pcm_buffer_bytes: int = 0) -> tuple[int, int, int, int, Iterator[list[int]]]:
+           stats=None, pcm_buffer_bytes: int = 0,
+           spec_wasted_bits: bool = False) -> tuple[int, int, int, int, Iterator[list[int]]]:
     """flac.decoder.decode (decoder.py:31-63): (sample_rate, sample_size, channels, samples,
     iterator of one list of ints per sample).  chunk_bytes: stream bytes per device call;
     pcm_buffer_bytes: the PCM staging buffer (0: sized by the first chunk; it grows when a frame
     does not fit and is drained in parts when a chunk's frames do not); stats: a list that
-    receives one dict per device call (the fields of flacmi_stream_result)."""
+    receives one dict per device call (the fields of flacmi_stream_result); spec_wasted_bits:
+    read a subframe's wasted bits as the format codes them and shift them back in
+    (FLACMI_DECODE_WASTED_SPEC; off: the reference's reading, which does neither)."""
     buffer, _ = _open(buffer)
     streaminfo = read_metadata(buffer)
 
     def samples() -> Iterator[list[int]]:
-        for chunk in _chunks(buffer, streaminfo, True, chunk_bytes, device, check_crc, stats, pcm_buffer_bytes):
+        for chunk in _chunks(buffer, streaminfo, True, chunk_bytes, device, check_crc, stats, pcm_buffer_bytes,
+                             spec_wasted_bits):
             yield from np.frombuffer(chunk, dtype="<i4").reshape(-1, streaminfo.channels).tolist()
 
     return (streaminfo.sample_rate, streaminfo.sample_size, streaminfo.channels, streaminfo.samples, samples())
 
 
 def decode_pcm(buffer_or_path, chunk_bytes: int = DEFAULT_CHUNK_BYTES, device: int = 0, check_crc: bool = False,
-               stats=None, pcm_buffer_bytes: int = 0) -> tuple[int, int, int, int, Iterator[bytes]]:
+               stats=None, pcm_buffer_bytes: int = 0,
+               spec_wasted_bits: bool = False) -> tuple[int, int, int, int, Iterator[bytes]]:
     """(sample_rate, sample_size, channels, samples, iterator of interleaved little-endian PCM
     chunks): what cmd_decode writes into the WAV (__main__.py:45-50), packed on the device."""
     buffer, owned = _open(buffer_or_path)
@@ -178,7 +184,8 @@ def decode_pcm(buffer_or_path, chunk_bytes: int = DEFAULT_CHUNK_BYTES, device: i
 
     def chunks() -> Iterator[bytes]:
         try:
-            yield from _chunks(buffer, streaminfo, False, chunk_bytes, device, check_crc, stats, pcm_buffer_bytes)
+            yield from _chunks(buffer, streaminfo, False, chunk_bytes, device, check_crc, stats, pcm_buffer_bytes,
+                               spec_wasted_bits)
         finally:
             if owned:
                 buffer.close()
@@ -187,11 +194,12 @@ def decode_pcm(buffer_or_path, chunk_bytes: int = DEFAULT_CHUNK_BYTES, device: i
 
 
 def decode_wav(path_in, path_out, device: int = 0, check_crc: bool = False,
-               chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> float:
+               chunk_bytes: int = DEFAULT_CHUNK_BYTES, spec_wasted_bits: bool = False) -> float:
     """cmd_decode (__main__.py:27-55): the WAV through the wave module; returns the seconds."""
     from wave import open as wave_open
     with open(path_in, "rb") as f, wave_open(str(path_out), mode="wb") as w:
-        (sample_rate, sample_size, channels, frames, chunks) = decode_pcm(f, chunk_bytes, device, check_crc)
+        (sample_rate, sample_size, channels, frames, chunks) = decode_pcm(f, chunk_bytes, device, check_crc,
+                                                                          spec_wasted_bits=spec_wasted_bits)
         w.setframerate(sample_rate)
         w.setsampwidth(sample_size // 8)
         w.setnchannels(channels)

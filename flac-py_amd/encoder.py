@@ -187,7 +187,7 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
            samples: Iterator[list], parameters: EncoderParameters, *, device: int = 0,
            devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 2048,
            fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
-           lpc_sign: bool = False) -> Iterator[bytes]:
+           lpc_sign: bool = False, wasted: bool = False) -> Iterator[bytes]:
     """flac/encoder.py:48-165 on the GPU: the per-channel analysis (k_lpc, k_resid) and
     the frame writer (k_frame.hip: Rice packing, headers, CRC-8/16), streamed through
     flacmi_encode_pipeline.  Only the stream header (magic + STREAMINFO) is written here.
@@ -208,9 +208,15 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
     is unchanged.  lpc_sign=True: the LPC candidates use the predictor and not its negation, as if
     the reference's levinson_durbin returned [-c for c in coefs[1:]] (include/flacmi.h
     FLACMI_FLAG_LPC_SIGN); LPC subframes then win on most signals.  It composes with fallback,
-    stereo and devices; with fixed_only=True it raises ValueError."""
+    stereo and devices; with fixed_only=True it raises ValueError.  wasted=True: a unit whose
+    samples share w zero low bits (16-bit audio in a 24-bit stream: w = 8) is analysed and written
+    as x >> w at sample_size - w bits behind a subframe header that declares w (include/flacmi.h
+    FLACMI_FRAME_WASTED); it composes with fallback, fixed_only, lpc_sign and devices, with
+    stereo=True it raises ValueError, and STREAMINFO is unchanged.  Such a stream is read with
+    decode(..., spec_wasted_bits=True); the reference's decoder misreads it."""
     _check_lpc_sign(lpc_sign, fixed_only)
     _check_stereo(stereo, channels)
+    _check_wasted(wasted, stereo)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, frames, parameters)
@@ -230,13 +236,13 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
             yield index, functools.partial(_planar, pending, channels, n)
 
     yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback,
-                      stereo)
+                      stereo, wasted)
 
 
 def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameters: EncoderParameters, *,
                   frames: Optional[int] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
                   blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False,
-                  stereo: bool = False, lpc_sign: bool = False) -> Iterator[bytes]:
+                  stereo: bool = False, lpc_sign: bool = False, wasted: bool = False) -> Iterator[bytes]:
     """encode() over planar PCM (int [channels][frames], e.g. from ingest.read_wav): the
     same bytes as encode(sample_rate, sample_size, channels, frames, <the frames of pcm>,
     parameters), without building a Python list per frame.  Blocks are cut straight into
@@ -246,6 +252,7 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
     channels, total = pcm.shape
     _check_lpc_sign(lpc_sign, fixed_only)
     _check_stereo(stereo, channels)
+    _check_wasted(wasted, stereo)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, total if frames is None else frames,
@@ -260,13 +267,13 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
             yield b0, functools.partial(planar_blocks, pcm, n, b0, bpb)
 
     yield from _drive(batches(), lambda: _sessions(device, devices), params, n, channels, sample_size, fallback,
-                      stereo)
+                      stereo, wasted)
 
 
 def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, device: int = 0,
                devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 0,
                fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
-               lpc_sign: bool = False) -> Iterator[bytes]:
+               lpc_sign: bool = False, wasted: bool = False) -> Iterator[bytes]:
     """The reference CLI's encode action (flac/__main__.py:58-109) on a WAV file, streamed:
     the stream header first, then frames batch by batch (ingest.iter_wav_pcm), so the host
     holds a bounded number of batches of PCM.  A reader failure (the reference's IndexError
@@ -276,6 +283,7 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
     _check_lpc_sign(lpc_sign, fixed_only)
     info = wav_info(path)
     _check_stereo(stereo, info.channels)
+    _check_wasted(wasted, stereo)
     if info.sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(info.sample_rate, info.sample_width * 8, info.channels, info.frames, parameters)
@@ -289,7 +297,7 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
 
     # sessions are opened after the first batch is read: a reader failure needs no device
     yield from _drive(batches(), lambda: _sessions(device, devices), params, n, C, info.sample_width * 8, fallback,
-                      stereo)
+                      stereo, wasted)
 
 
 def _check_lpc_sign(lpc_sign: bool, fixed_only: bool) -> None:
@@ -302,6 +310,12 @@ def _check_stereo(stereo: bool, channels: int) -> None:
     """stereo=True needs two channels; refused before any device work."""
     if stereo and channels != 2:
         raise ValueError(f"stereo decorrelation needs 2 channels, the input has {channels}")
+
+
+def _check_wasted(wasted: bool, stereo: bool) -> None:
+    """wasted=True with stereo=True is not built (a follow-up); refused before any device work."""
+    if wasted and stereo:
+        raise ValueError("wasted bits and stereo decorrelation do not combine yet")
 
 
 def _stream_header(sample_rate, sample_size, channels, frames, parameters):
@@ -352,7 +366,7 @@ class _Session:
         return buf[:nbytes].view(dtype).reshape(shape)
 
     def encode(self, rows, bits, tail_len, n_tail, params, n, channels, sample_size, first_frame,
-               fallback: bool = False, stereo: bool = False):
+               fallback: bool = False, stereo: bool = False, wasted: bool = False):
         """-> (frame bytes, offsets, status) of one batch (host copies: the buffers are reused)."""
         cap = int(rows.shape[0] * (n * rows.itemsize * 1.25 + 256)) + (1 << 20)
         while True:
@@ -363,7 +377,7 @@ class _Session:
                 data, offsets, status, _ = self.az.encode_pipeline(
                     rows, params, n, tail_len, n_tail, sample_bits=bits, channels=channels,
                     sample_size=sample_size, first_frame=first_frame, units_per_batch=_SUB_UNITS,
-                    out=self.out, fallback=fallback, stereo=stereo)
+                    out=self.out, fallback=fallback, stereo=stereo, wasted=wasted)
             except FlacmiError as e:
                 if e.code == abi.E_NOMEM:
                     cap = 2 * max(cap, self.out.size)
@@ -417,7 +431,8 @@ def _release(sessions) -> None:
         s.close()
 
 
-def _drive(batches, sessions, params, n, channels, sample_size, fallback=False, stereo=False) -> Iterator[bytes]:
+def _drive(batches, sessions, params, n, channels, sample_size, fallback=False, stereo=False,
+           wasted=False) -> Iterator[bytes]:
     """batches yields (first_block, cut) with cut(alloc=...) -> (rows, bits, tail_len,
     n_tail_units); batch i goes to sessions[i % D].  Frames are yielded in block order; a
     frame the reference would fail on raises its exception after the frames before it, and
@@ -451,7 +466,7 @@ def _drive(batches, sessions, params, n, channels, sample_size, fallback=False, 
                 failure = e
                 break
             queue.append(s.pool.submit(s.encode, rows, bits, tail_len, n_tail, params, n, channels, sample_size,
-                                       first_block, fallback, stereo))
+                                       first_block, fallback, stereo, wasted))
             i += 1
         while queue:
             yield from _frames(*queue.popleft().result())

@@ -157,7 +157,7 @@ def frame_report(index: int, base: int, rec, subs, parts) -> FrameReport:
 
 
 def _frames(report: StreamReport, buffer, owned: bool, chunk_bytes: int, device: int, max_partitions: int,
-            frame_capacity: int) -> Iterator[FrameReport]:
+            frame_capacity: int, spec_wasted_bits: bool = False) -> Iterator[FrameReport]:
     """The FrameReports of the frames at `buffer`'s position, one flacmi_info_stream_host call
     per chunk (decoder._chunks' carry-over of a cut-off frame)."""
     si = report.streaminfo
@@ -185,7 +185,8 @@ def _frames(report: StreamReport, buffer, owned: bool, chunk_bytes: int, device:
             if stage is None or n > len(stage):
                 stage = az.host_array((n,), np.uint8)
             stage[:n] = np.frombuffer(data, dtype=np.uint8)
-            res = az.info_stream(stage.ctypes.data, n, 0, si.channels, si.sample_size, final, frames, subs, parts)
+            res = az.info_stream(stage.ctypes.data, n, 0, si.channels, si.sample_size, final, frames, subs, parts,
+                                 spec_wasted_bits)
             report.stats.append({f: getattr(res, f) for f, _ in abi.InfoResult._fields_} | {"bytes": n, "final": final})
             for k in range(res.frames):
                 yield frame_report(index + k, base, frames[k], subs[k], parts[k])
@@ -209,10 +210,13 @@ def _frames(report: StreamReport, buffer, owned: bool, chunk_bytes: int, device:
 
 
 def analyze(buffer_or_path, chunk_bytes: int = DEFAULT_CHUNK_BYTES, device: int = 0, max_partitions: int = 64,
-            frame_capacity: int = FRAME_CAPACITY) -> StreamReport:
+            frame_capacity: int = FRAME_CAPACITY, spec_wasted_bits: bool = False) -> StreamReport:
     """The report of a FLAC stream (a path, bytes or a binary file object).  chunk_bytes: stream
     bytes per device call; max_partitions: Rice parameters kept per subframe (a subframe with
-    more is marked `truncated`); frame_capacity: frame records per device call."""
+    more is marked `truncated`); frame_capacity: frame records per device call; spec_wasted_bits:
+    read wasted bits as the format codes them (FLACMI_DECODE_WASTED_SPEC), so a subframe's
+    wasted_bits is the count its encoder declared and sample_bits the width it wrote (off: the
+    reference's reading, one less wasted bit and one more sample bit in a flagged subframe)."""
     buffer, owned = _open(buffer_or_path)
     try:
         streaminfo, blocks = read_blocks(buffer)
@@ -221,7 +225,8 @@ def analyze(buffer_or_path, chunk_bytes: int = DEFAULT_CHUNK_BYTES, device: int 
             buffer.close()
         raise
     report = StreamReport(streaminfo=streaminfo, metadata=blocks, first_frame_offset=buffer.tell(), frames=iter(()))
-    report.frames = _frames(report, buffer, owned, chunk_bytes, device, max_partitions, max(frame_capacity, 1))
+    report.frames = _frames(report, buffer, owned, chunk_bytes, device, max_partitions, max(frame_capacity, 1),
+                            spec_wasted_bits)
     return report
 
 

@@ -50,7 +50,12 @@ extern "C" {
       but 0 and 1 is refused; flacmi_stereo_rows_device is new; version 3 callers passed 0 there
       and see no change
    5: flacmi_params.reserved[1] takes FLACMI_FLAG_LPC_SIGN (the corrected LPC predictor sign, off by
-      default); version 4 callers never set bit 2 there and see no change */
+      default); version 4 callers never set bit 2 there and see no change
+   6: the stream analysis (flacmi_frame_info_device, flacmi_info_stream_host).  Added since, at
+      the same version (no struct changes size): flacmi_wasted_rows_device, FLACMI_FRAME_WASTED in
+      flacmi_frame_params.reserved0, and flacmi_decode_params.reserved0 carries the decode flags
+      (FLACMI_DECODE_WASTED_SPEC); a value with unknown bits is refused, callers that passed 0 there
+      see no change */
 #define FLACMI_ABI_VERSION 6
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
@@ -293,13 +298,35 @@ int flacmi_analyze_host(flacmi_ctx* ctx, const flacmi_batch* batch,
  * candidates are both eligible; its header carries that code and its side subframe is written
  * at ss + 1 bits.  With no eligible assignment the frame fails with the status the L_R frame has
  * without the mode.  FLACMI_STATUS_RESIDUAL_WIDE on any candidate fails the frame with that status
- * (the redo with 8-byte residual rows still happens); the frame-level failures are unchanged. */
+ * (the redo with 8-byte residual rows still happens); the frame-level failures are unchanged.
+ *
+ * Wasted bits (FLACMI_FRAME_WASTED, off by default; with it off every byte, status and launch is as
+ * without it).  The reference's SubframeHeader carries wasted_bits (common.py:309) and every
+ * encoder path writes 0 (encoder.py:326, :556).  The mode is honoured by flacmi_encode_host and
+ * flacmi_encode_pipeline, which own their device copy of the rows; the *_device frame entry points
+ * have no free slot for the array and refuse the bit.  For a unit of n samples x_i at the
+ * stream's sample size ss, with m the bitwise OR of all x_i in two's complement: w = 0 when
+ * m == 0 (digital silence has no wasted bits, as in libFLAC), otherwise w = ctz(m) clamped to
+ * ss - 1 (flacmi_wasted_rows_device, below).  The unit is analysed and written as the unit holding
+ * x_i >> w (arithmetic shift, exact) at ss - w bits: same parameters, pruning, status, site,
+ * FIXED / LPC choice and Rice search as a channel holding those samples (the reference's
+ * per-channel analysis never looks at the sample size).  Its subframe header is 0 tttttt 0 when
+ * w == 0, as without the mode, and 0 tttttt 1, w - 1 zero bits and a one when w > 0 (8 + w bits);
+ * warm-up, CONSTANT and VERBATIM samples are written at ss - w bits.  With FLACMI_FRAME_FALLBACK a
+ * unit is escaped when its exact size exceeds its own VERBATIM size 8 + w + n (ss - w); CONSTANT
+ * writes x_0 >> w; every other fallback rule is unchanged.  Every frame of such a batch goes
+ * through the general writer.  It composes with FLACMI_FRAME_FALLBACK, FLACMI_MODE_FIXED_ONLY and
+ * FLACMI_FLAG_LPC_SIGN; together with FLACMI_STEREO_BEST the call returns FLACMI_E_INVALID (a
+ * follow-up).  batch.sample_bits stays an upper bound: kernel dispatch is unchanged.  STREAMINFO
+ * is unchanged.  A decoder reads such a stream with FLACMI_DECODE_WASTED_SPEC (the reference's own
+ * decoder cannot). */
 enum flacmi_stereo_mode {
     FLACMI_STEREO_OFF = 0,
     FLACMI_STEREO_BEST = 1,
 };
 enum flacmi_frame_flags {
     FLACMI_FRAME_FALLBACK = 1,
+    FLACMI_FRAME_WASTED = 4, /* not 2: callers and tests/test_gpu_fallback.py rely on bit 1 being refused */
 };
 /* per-unit decision of the fallback mode (sub_kind[u]) */
 enum flacmi_sub_kind {
@@ -358,6 +385,25 @@ int flacmi_encode_fetch(flacmi_ctx* ctx, uint8_t* out, int64_t bytes);
  * aligned, every pitch a multiple of 16 bytes and at least block_len elements. */
 int flacmi_stereo_rows_device(flacmi_ctx* ctx, const flacmi_batch* lr, void* mid, int64_t mid_stride,
                               int32_t* side, int64_t side_stride, void* stream);
+
+/* The wasted bits of every unit of a batch and the units without them (device pointers, enqueued
+ * on `stream`).  FLAC lets a subframe declare k wasted bits: the k low bits that are zero in every
+ * sample of the block, shifted out before prediction and shifted back in by the decoder; the
+ * reference's SubframeHeader carries the field (common.py:309) and each of its encoder paths writes
+ * 0 (encoder.py:326, :556).  The rule, for a unit of n samples x_i of in->sample_bits bits (int16
+ * or int32 rows; the last n_tail_units units hold tail_len samples): with m the bitwise OR of all
+ * x_i in two's complement, w = 0 when m == 0 (digital silence has no wasted bits, as in libFLAC),
+ * otherwise w = ctz(m), clamped to sample_bits - 1.  wasted[u] receives w and row u of out_rows
+ * (in's element type, a pitch of out_stride elements) receives x_i >> w (arithmetic shift, exact):
+ * the unit a subframe of width sample_bits - w is analysed and written from.  Nothing at or past a
+ * unit's length is read or written.  out_rows may equal in->samples (out_stride then equals
+ * in->unit_stride): the rows are shifted in place and a unit with w == 0 is not stored, so a
+ * batch without wasted bits costs one read of its samples; any other overlap is undefined.  Every
+ * row must be 16-byte aligned, every pitch a multiple of 16 bytes and at least block_len elements.
+ * This is the first step of FLACMI_FRAME_WASTED, which the host entry points run in place on
+ * their own copy of the rows. */
+int flacmi_wasted_rows_device(flacmi_ctx* ctx, const flacmi_batch* in, void* out_rows, int64_t out_stride,
+                              int32_t* wasted, void* stream);
 
 /* Pipelined host encode (SURVEY §8d end-to-end; the reference's encode() loop plus its
  * writer, encoder.py:87-165, 765-806): host sample rows in, FLAC frame bytes out, the batch
@@ -423,7 +469,23 @@ int flacmi_host_free(flacmi_ctx* ctx, void* ptr);
  * the reference on every valid frame, with two documented choices: an L_R frame holds
  * dp->channels subframes (encoder.py:95 writes L_R whatever the channel count, so the
  * reference decoder cannot read back its own mono or 3+ channel streams), and, as in
- * decode_subframe, wasted bits are parsed but not shifted back in. */
+ * decode_subframe, wasted bits are parsed but not shifted back in.
+ *
+ * Wasted bits as the format codes them (FLACMI_DECODE_WASTED_SPEC in dp->reserved0, off by
+ * default; with it off every sample, status and frame end is as above).  A subframe whose header
+ * ends in a set flag bit codes k wasted bits as k - 1 zeros and a one.  The reference reads them
+ * wrongly twice: get_wasted_bits (decoder.py:346-355) returns the number of zeros, k - 1, and
+ * decode_subframe never shifts the samples back (get_subframe drops the header).  With the flag
+ * (a) wasted = zeros + 1, so the subframe's sample width is ss + (1 for a side channel) - wasted
+ * (a width <= 0 keeps FLACMI_DSITE_ESCAPE_ZERO), and (b) every restored sample of the subframe is
+ * s << wasted before the comparison with `expect`, before stereo recombination and before the
+ * PCM range check.  The parse, and so the frame's end, differs between the two readings: the flag
+ * reaches every pass that parses frames (the stream decoder's two passes and probes, the chain
+ * walk through their ends, flacmi_frame_info_device / flacmi_info_stream_host, which then report
+ * wasted_bits = k and sample_bits accordingly).  Any other bit of reserved0: FLACMI_E_INVALID. */
+enum flacmi_decode_flags {
+    FLACMI_DECODE_WASTED_SPEC = 1,
+};
 #define FLACMI_STATUS_EOF 5        /* EOFError: the frame runs past the end of the stream */
 #define FLACMI_STATUS_VERIFY 18    /* verifier finding (not a reference exception) */
 enum flacmi_decode_site {
@@ -456,7 +518,7 @@ typedef struct flacmi_decode_params {
     int32_t sample_size;     /* STREAMINFO sample size, used when the header defers to it, 4..32 */
     int64_t first_frame;     /* coded number expected for frame 0, or -1: not checked */
     int32_t check_crc;       /* 1: verify CRC-8 and CRC-16 (the reference reads them unchecked) */
-    int32_t reserved0;
+    int32_t reserved0;       /* enum flacmi_decode_flags bits (the name predates them); any other bit: FLACMI_E_INVALID */
     int64_t reserved[2];
 } flacmi_decode_params;
 /* All pointers are device pointers; the work is enqueued on `stream`.  stream_bytes is the
