@@ -530,6 +530,9 @@ static int prune_allowed() {
  * 0 = no overlap; k > 1 = up to k equal chunks of at least kOverlapMinUnits; -R (R > 1) =
  * round-aligned with R units per round and no minimum (tests). */
 constexpr int64_t kOverlapMinUnits = 16384;
+#ifndef FLACMI_CLASS_LISTS
+#define FLACMI_CLASS_LISTS 1 /* A/B build (timing only, same results): 0 runs every chunk's list passes behind its batch kernel */
+#endif
 static int overlap_mode() { return knob(kKnobOverlap); }
 
 static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const flacmi_params* p,
@@ -634,8 +637,9 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         a.acf = o->acf ? o->acf + k.unit0 * 33 : nullptr;
         return 0;
     };
-    auto launch_resid_chunk = [&](const Chunk& k, hipStream_t st) -> hipError_t {
-        ResidArgs a{};
+    /* the residual pass's arguments for units [k.unit0, k.unit0 + k.count) and the path it takes */
+    auto resid_args = [&](const Chunk& k, ResidArgs& a, int& path) -> hipError_t {
+        a = ResidArgs{};
         a.samples = b->samples;
         a.stride = b->unit_stride;
         a.unit0 = k.unit0;
@@ -678,8 +682,14 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         }
         a.sign_bound = !(p->reserved[1] & FLACMI_FLAG_TIERS_ONLY) && sign_bound_allowed();
         const bool wide = needs_wide(k.n, b->sample_bits, L, p->qlp_precision, p->mode);
-        int path = (wide || o->residual_bytes == 8) ? 2 : (b->sample_bytes == 2 && p->qlp_precision <= 16) ? 0 : 1;
+        path = (wide || o->residual_bytes == 8) ? 2 : (b->sample_bytes == 2 && p->qlp_precision <= 16) ? 0 : 1;
         if (path == 2 && o->residual_bytes == 4 && split_ok(b->sample_bits, L, p->qlp_precision)) path = 3;
+        return hipSuccess;
+    };
+    auto launch_resid_chunk = [&](const Chunk& k, hipStream_t st) -> hipError_t {
+        ResidArgs a;
+        int path = 0;
+        if (hipError_t e = resid_args(k, a, path); e != hipSuccess) return e;
         return launch_resid(a, path, o->residual_bytes, st);
     };
     const int slot = ctx->ncalls % flacmi_ctx::kRing;
@@ -707,11 +717,35 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
             HIP_TRY(hipEventRecord(ctx->lpc_done[i], side));
         }
         HIP_TRY(hipEventRecord(ev[1], side));
-        for (int i = 0; i < nch; ++i) {
-            HIP_TRY(hipStreamWaitEvent(s, ctx->lpc_done[i], 0));
-            HIP_TRY(hipEventRecord(ev[3 + 2 * i], s));
-            HIP_TRY(launch_resid_chunk(ch[i], s));
-            HIP_TRY(hipEventRecord(ev[4 + 2 * i], s));
+        for (int i = 0; i < nch;) {
+            /* the chunks [i, j) of one length class.  Where they take k_resid_stream's pre-test build,
+             * their batch kernels run back to back (the counters zeroed once, ids listed relative to
+             * the class) and one list pass and one retry pass follow the last: no list launch, retry
+             * kernel or memset drains the GPU between two batch kernels.  Each chunk's timing span
+             * holds its batch kernel, the first's the memsets too, the last's both list passes. */
+            int j = i + 1;
+            while (j < nch && ch[j].n == ch[i].n && ch[j].unit0 == ch[j - 1].unit0 + ch[j - 1].count) ++j;
+            ResidArgs ca;
+            int cpath = 0;
+            const Chunk whole{ch[i].unit0, ch[j - 1].unit0 + ch[j - 1].count - ch[i].unit0, ch[i].n};
+            HIP_TRY(resid_args(whole, ca, cpath));
+            const bool merged = FLACMI_CLASS_LISTS && j - i > 1 && stream_class_ok(ca, cpath, o->residual_bytes);
+            for (int c = i; c < j; ++c) {
+                HIP_TRY(hipStreamWaitEvent(s, ctx->lpc_done[c], 0));
+                HIP_TRY(hipEventRecord(ev[3 + 2 * c], s));
+                if (merged) {
+                    ResidArgs a;
+                    int path = 0;
+                    HIP_TRY(resid_args(ch[c], a, path));
+                    if (c == i) HIP_TRY(launch_stream_class_begin(ca, s));
+                    HIP_TRY(launch_stream_class_batch(a, ch[c].unit0 - whole.unit0, whole.count, s));
+                    if (c == j - 1) HIP_TRY(launch_stream_class_lists(ca, s));
+                } else {
+                    HIP_TRY(launch_resid_chunk(ch[c], s));
+                }
+                HIP_TRY(hipEventRecord(ev[4 + 2 * c], s));
+            }
+            i = j;
         }
     } else {
         for (int i = 0; i < nch && lpc; ++i) {

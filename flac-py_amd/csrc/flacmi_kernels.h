@@ -93,6 +93,8 @@ struct ResidArgs {
     const uint16_t* chunk_weight;    /* [n / 8] floor(256 min window weight) per 8-sample chunk (NULL: no pre-test) */
     int32_t energy;                  /* knob FLACMI_ENERGY_BOUND: 1 = pre-test, then the tiers; 2 = pre-test, then
                                         the exact pass; 0 = the tiers alone */
+    int64_t list_off;                /* k_resid_stream's pre-test build lists unit gid as gid + list_off (set by
+                                        the launchers: launch_stream_class_batch) */
 };
 /* internal unit status between the fast and the generic k_resid (never returned) */
 #define FLACMI_STATUS_RETRY 0x7e
@@ -284,6 +286,12 @@ hipError_t launch_export(const int64_t* off, const int32_t* st, int64_t nf, int6
 hipError_t launch_lpc_from_acf(const LpcArgs& a, hipStream_t s);
 /* path: 0 = int16 samples / sdot2, 1 = int32 samples / mad24, 2 = int64 arithmetic */
 hipError_t launch_resid(const ResidArgs& a, int path, int residual_bytes, hipStream_t s);
+/* k_resid_stream over the chunks of one length class (k_stream.hip): begin, every chunk's batch
+ * kernel, then the list passes once */
+bool stream_class_ok(const ResidArgs& cls, int path, int residual_bytes);
+hipError_t launch_stream_class_begin(const ResidArgs& cls, hipStream_t s);
+hipError_t launch_stream_class_batch(const ResidArgs& chunk, int64_t list_off, int64_t class_count, hipStream_t s);
+hipError_t launch_stream_class_lists(const ResidArgs& cls, hipStream_t s);
 hipError_t launch_expand_records(const int32_t* rec, int32_t rec_words, int32_t L, int64_t count,
                                  int32_t* out, hipStream_t s);
 hipError_t launch_synth(void* dst, int32_t sample_bytes, int32_t bits, int64_t stride,

@@ -23,7 +23,9 @@
  *     predictors (shift 0): |r| is one v_sad_u32; LPC: one shift + one v_sad_u32.
  *     MFMA 0 holds fixed orders 1..4 x 4 sample phases, MFMAs 1..NG the LPC orders
  *     4(g-1)+1 .. 4g x 4 phases; each lane builds its B operands from the LDS record (the
- *     fixed group's is a constant).  Units outside the bound are listed for k_resid;
+ *     fixed group's is a constant).  The energy bound's pre-test build runs the fixed group on
+ *     its own at row stride 8: two MFMAs (orders 1-2, 3-4 x 8 phases) on one A operand per 128
+ *     samples (fixed8).  Units outside the bound are listed for k_resid;
  *   - the choice (a lane-parallel DPP argmin), the Rice parameters (one heap node per lane,
  *     finest partition sums by LDS atomics) and the order choice are
  *     computed redundantly by every wave from LDS data, so no single-wave serial section
@@ -57,6 +59,12 @@ constexpr int kSCPT = FLACMI_STREAM_CPT; /* max 8-sample chunks per thread */
 #endif
 #ifndef FLACMI_SAD16
 #define FLACMI_SAD16 1 /* staging's sum|x| on v_sad_u16 */
+#endif
+#ifndef FLACMI_FIXED_STRIDE8
+#define FLACMI_FIXED_STRIDE8 1 /* pre-test build: fixed group at row stride 8, two B operands per A */
+#endif
+#ifndef FLACMI_ENTRY_LOADS
+#define FLACMI_ENTRY_LOADS 1 /* pre-test build: the status word and k_lpc's two words loaded at kernel entry */
 #endif
 /* workgroup size: 8-sample chunks, up to kSCPT per thread */
 __host__ __device__ constexpr int stream_threads(int n) {
@@ -144,6 +152,30 @@ constexpr FixB make_fixb() {
     return t;
 }
 __constant__ const FixB kFixB = make_fixb();
+/* The stride-8 fixed group (FLACMI_FIXED_STRIDE8: the energy bound's pre-test builds, whose fixed
+ * loop shares no A operand with an LPC group): MFMA rows 8 samples apart, row m's
+ * window samples 8m - 8 .. 8m + 7 of a 128-sample step, and two B operands on the same A.  Table t
+ * holds orders 2t + 1 and 2t + 2: column = 8 (order index) + phase rho (0..7), and ia = 8 + rho -
+ * 4 kb <= 15, so the window holds taps 0..4 at every phase. */
+constexpr FixB make_fixb8(int t) {
+    FixB b{};
+    for (int l = 0; l < 64; ++l) {
+        const int col = l & 15, kb = l >> 4, p = 2 * t + (col >> 3) + 1, rho = col & 7, ia = 8 + rho - 4 * kb;
+        const int idx[2] = {ia, ia - 2};
+        for (int k = 0; k < 2; ++k) {
+            const int i = idx[k];
+            b.w[4 * l + k] = f16_bits(256 * fixed_tap(p, i)) | f16_bits(256 * fixed_tap(p, i - 1)) << 16;
+            b.w[4 * l + 2 + k] = f16_bits(fixed_tap(p, i)) | f16_bits(fixed_tap(p, i - 1)) << 16;
+        }
+    }
+    return b;
+}
+__constant__ const FixB kFixB8a = make_fixb8(0);
+__constant__ const FixB kFixB8b = make_fixb8(1);
+/* (a function, for the use inside a lambda: a lambda that names the variable itself makes the
+ * compiler give the table external linkage, and every kernel then loads its address through the
+ * GOT, a dependent scalar load in front of staging's table load) */
+__device__ __forceinline__ uint4 fixb_of(uint32_t lane) { return reinterpret_cast<const uint4*>(kFixB.w)[lane]; }
 
 /* |a - b| + acc: the compiler emits one v_sad_u32 when b is in a VGPR (opaque() keeps a
  * constant b there).  Not inline asm: the hazard recognizer does not see an asm operand
@@ -367,11 +399,25 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
     uint16_t* pkw = reinterpret_cast<uint16_t*>(smem + lay.pk);
     flacmi_unit_meta* meta = a.meta + gid;
     MetaVals mv{};
+    /* S8: the fixed group at row stride 8 (kFixB8a/b), in the pre-test build, whose fixed loop is a
+     * loop of its own.  (The fixed-only build shares no A operand either, but config 5 is bound by
+     * HBM, not by VALU issue: measured with it, 0.02 ms per step slower in 4 of 5 rounds) */
+    constexpr bool S8 = FLACMI_FIXED_STRIDE8 && EB;
+    /* EB: the record's status word and k_lpc's two words, workgroup-uniform and read before any
+     * store or barrier of the kernel: scalar loads that land during staging (used after B1) */
+    constexpr bool EL = FLACMI_ENTRY_LOADS && EB;
+    int st_entry = 0;
+    uint2 bw_entry{0u, 0u};
+    if constexpr (EL) {
+        st_entry = (a.rec + gid * rw)[0];
+        bw_entry = *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
+    }
 
     /* ---- stage: biased samples and the record into LDS, sum|x| on the way (EB: no record
      * here; a unit its pre-test does not decide builds the tap table then) ---- */
     constexpr int kTW = tap_table_words(NG), kTJ = NG > 0 ? (kTW + 63) / 64 : 0;
-    uint4 fixb; /* the fixed group's MFMA B operand (constant) */
+    uint4 fixb{};  /* the fixed group's MFMA B operand (constant) */
+    uint4 fixb8[2]{}; /* S8: its two operands */
     {
         const uint4* src = reinterpret_cast<const uint4*>((const int16_t*)a.samples + (a.unit0 + gid) * a.stride);
         /* every load is issued before the first wait: clamped indices, no branches (a load
@@ -387,7 +433,17 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
             q[j] = src[min(tid + j * NT, nch - 1)];
 #endif
         }
-        fixb = reinterpret_cast<const uint4*>(kFixB.w)[lane];
+        if constexpr (S8) {
+            fixb8[0] = reinterpret_cast<const uint4*>(kFixB8a.w)[lane];
+            fixb8[1] = reinterpret_cast<const uint4*>(kFixB8b.w)[lane];
+        } else {
+            fixb = reinterpret_cast<const uint4*>(kFixB.w)[lane];
+        }
+        if constexpr (EL) { /* opaque, behind the sample loads' issue: the entry loads are not sunk to their use behind B1 */
+            st_entry = (int)opaque_s((uint32_t)st_entry);
+            bw_entry.x = opaque_s(bw_entry.x);
+            bw_entry.y = opaque_s(bw_entry.y);
+        }
         uint32_t cwv[EB ? kSCPT : 1]; /* the chunks' weights (1/256) */
         if constexpr (EB) {
 #pragma unroll
@@ -477,7 +533,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
     uint32_t negmask = 0;
     const int32_t* __restrict__ grec = NG > 0 ? a.rec + gid * rw : nullptr; /* wave-uniform: scalar loads */
     if constexpr (NG > 0) {
-        const int st = grec[0];
+        const int st = EL ? st_entry : grec[0];
         if (st != 0) { /* the reference raises inside encode_subframe_lpc */
             if (wid == 0) {
                 mv.status = st & 0xffff;
@@ -492,7 +548,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
      * MFMA bound, so it will be listed below and its fixed sums would be thrown away: the fixed
      * group is skipped */
     uint2 bw{0u, 0u};
-    if constexpr (EB) bw = *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
+    if constexpr (EB) bw = EL ? bw_entry : *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
     const bool listed = EB && bw.x == kBoundUnusable && bw.y == kBoundOutside;
 
     /* ---- candidate sums on MFMA ----
@@ -691,14 +747,87 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
         using ING = std::integral_constant<int, NG>;
+        /* S8: the fixed group over the whole unit, then its sums into the fixed group's red64 slots.
+         * A step is 128 samples: lane (m, kb) loads samples 8m - 8 + 4kb .. + 3 of it as A, both
+         * MFMAs (orders {1,2}, {3,4}) take that A, and the lane's value r of table t is sample
+         * 8 (4kb + r) + rho8 at order 2t + o8 + 1.  The wave's steps are wid, wid + nw, ... two per
+         * iteration (both loads before the first wait); wave 0 takes step 0 last, masked (warm-up
+         * samples i < order).  n % 128 == 64 (runtime-shape builds): the last 64 samples run the
+         * 4-phase block on one wave, and its sums are added to the same slots. */
+        auto fixed8 = [&]() __attribute__((always_inline)) {
+            const int o8 = col >> 3, rho8 = col & 7, nstep = n >> 7;
+            const h8 B8[2] = {__builtin_bit_cast(h8, fixb8[0]), __builtin_bit_cast(h8, fixb8[1])};
+            uint32_t acc8[2] = {0u, 0u};
+            const int eoff8 = 8 * (lane & 15) - 8 + 4 * kb;
+            auto ld8 = [&](int st) __attribute__((always_inline)) {
+                return *reinterpret_cast<const uint2*>(xs + 128 * st + eoff8);
+            };
+            auto step8 = [&](const uint4 Ar, bool masked) __attribute__((always_inline)) {
+                f4 D[2];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) D[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, Ar), B8[t], C, 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const uint32_t bits = __float_as_uint(D[t][r]);
+                        if (masked) {
+                            const int i = 8 * (4 * kb + r) + rho8; /* step 0 */
+                            acc8[t] += i >= 2 * t + o8 + 1 ? sad32(bits, mbv, 0u) : 0u;
+                        } else {
+                            acc8[t] = opaque(sad32(bits, mbv, acc8[t]));
+                        }
+                    }
+                }
+            };
+            int st = wid == 0 ? nw : wid;
+            for (; st + nw < nstep; st += 2 * nw) {
+                const uint2 q0 = ld8(st), q1 = ld8(st + nw);
+                step8(a_raw(q0), false);
+                step8(a_raw(q1), false);
+            }
+            if (st < nstep) step8(a_raw(ld8(st)), false);
+            if (wid == 0 && nstep > 0) { /* (the address from the thread id again, as ld0) */
+                const uint32_t t = opaque((uint32_t)tid);
+                step8(a_raw(*reinterpret_cast<const uint2*>(xs + 8 * (int)(t & 15) - 8 + 4 * (int)((t >> 4) & 3))), true);
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) { /* 8 phases (< 2^32), then in 64 bits the 4 kb rows */
+                uint32_t v = acc8[t];
+                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);
+                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);
+                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false); /* row_half_mirror */
+                uint64_t w = v;
+                w += (uint64_t)(uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); /* lane ^ 16 */
+                w += __shfl_xor((unsigned long long)w, 32);
+                if (rho8 == 0 && kb == 0) red64[(wid * 4 + 0) * 4 + 2 * t + o8] = w;
+            }
+            if ((n & 64) && wid == nstep % nw) {
+                const uint32_t t = opaque((uint32_t)tid);
+                B[0] = __builtin_bit_cast(h8, fixb_of(t & 63));
+                const uint2 q = *reinterpret_cast<const uint2*>(xs + 64 * (nblk - 1) + 4 * (int)(t & 15) - 12 + 4 * (int)((t >> 4) & 3));
+                blockA(I0{}, I0{}, I0{}, a_raw(q), nblk == 1, xnone);
+                uint32_t v = acc[0];
+                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);
+                v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);
+                uint64_t w = v;
+                w += (uint64_t)(uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
+                w += __shfl_xor((unsigned long long)w, 32);
+                if (rho == 0 && kb == 0) red64[(wid * 4 + 0) * 4 + o4] += w; /* (behind this wave's stores above) */
+            }
+        };
         /* this wave's blocks wid + k nw, k = 0 .. kw - 1 (wave 0 takes block 0 masked, last) */
         const int kw = (nblk - wid + nw - 1) / nw;
         if (EB && prune) {
             /* the fixed group alone over every block: the pre-test below needs the fixed sums */
             if (!listed) {
-                for (int k = wid == 0 ? 1 : 0; k < kw; ++k) blockA(I0{}, I0{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
-                if (wid == 0) block(I0{}, I0{}, I0{}, ld0(), true, 0);
-                reduce_store(I0{}, I0{}, I0{});
+                if constexpr (S8) {
+                    fixed8();
+                } else {
+                    for (int k = wid == 0 ? 1 : 0; k < kw; ++k) blockA(I0{}, I0{}, I0{}, a_raw(ld(wid + k * nw)), false, xnone);
+                    if (wid == 0) block(I0{}, I0{}, I0{}, ld0(), true, 0);
+                    reduce_store(I0{}, I0{}, I0{});
+                }
             }
         } else if (prune) {
             /* tier 0: the wave's blocks k % 4 == 0 run the LPC groups (bound) beside the fixed
@@ -803,11 +932,14 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                         /* (listed without outside cannot happen, see k_lpc's lpc_finish; the unit has no
                          * fixed sums, and the list kernel computes any unit exactly) */
                         if (__ballot(outside) || listed) {
-                            if (tid == 0) { /* sub-list gid & 63, as above */
+                            if (tid == 0) { /* sub-list id & 63, as above; the id counts from the length class's
+                                             * first unit (a.list_off: this chunk's place in it), see
+                                             * launch_stream_class_lists */
                                 meta->status = FLACMI_STATUS_RETRY;
-                                const int r = (int)(gid & 63);
+                                const int64_t id = gid + a.list_off;
+                                const int r = (int)(id & 63);
                                 const unsigned long long k = atomicAdd(a.retry_sub + 16 * r, 1ull);
-                                a.retry_list[r * a.retry_sub_cap + (int64_t)k] = gid;
+                                a.retry_list[r * a.retry_sub_cap + (int64_t)k] = id;
                             }
                             return;
                         }
@@ -1425,16 +1557,10 @@ static hipError_t launch_stream_G(const ResidArgs& a, bool list, hipStream_t s) 
     return launch_stream_T<3>(a, list, s);
 }
 
-/* the batch, then (reference mode) the units it listed through the list kernel (pred-only
- * taps), then the units that one listed through k_resid's list variant */
-hipError_t launch_resid_stream(const ResidArgs& a_in, hipStream_t s) {
-    ResidArgs a = a_in;
-    a.retry_sub_cap = (a.count + 63) / 64; /* sub-list u & 63 holds at most ceil(count / 64) units */
-    hipError_t e = hipMemsetAsync(a.retry_sub, 0, 64 * 16 * sizeof(unsigned long long), s);
-    if (e != hipSuccess) return e;
-    if ((e = launch_stream_G(a, false, s)) != hipSuccess) return e;
-    if (a.mode == FLACMI_MODE_FIXED_ONLY) return hipSuccess; /* nothing is ever listed */
-    if ((e = hipMemsetAsync(a.retry2_count, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+/* the units the batch kernel listed through the list kernel (pred-only taps), then the units
+ * that one listed through k_resid's list variant */
+static hipError_t launch_stream_lists(const ResidArgs& a, hipStream_t s) {
+    hipError_t e;
     if ((e = launch_poison_lds(s)) != hipSuccess) return e;
     if ((e = launch_stream_G(a, true, s)) != hipSuccess) return e;
     if ((e = launch_poison_lds(s)) != hipSuccess) return e;
@@ -1442,6 +1568,48 @@ hipError_t launch_resid_stream(const ResidArgs& a_in, hipStream_t s) {
     b.retry_count = a.retry2_count;
     b.retry_list = a.retry2_list;
     return a.L <= 8 ? launch_resid_retry_l8(b, s) : launch_resid_retry_l12(b, s);
+}
+
+/* the batch, then (reference mode) the two list passes */
+hipError_t launch_resid_stream(const ResidArgs& a_in, hipStream_t s) {
+    ResidArgs a = a_in;
+    a.list_off = 0;
+    a.retry_sub_cap = (a.count + 63) / 64; /* sub-list u & 63 holds at most ceil(count / 64) units */
+    hipError_t e = hipMemsetAsync(a.retry_sub, 0, 64 * 16 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    if ((e = launch_stream_G(a, false, s)) != hipSuccess) return e;
+    if (a.mode == FLACMI_MODE_FIXED_ONLY) return hipSuccess; /* nothing is ever listed */
+    if ((e = hipMemsetAsync(a.retry2_count, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    return launch_stream_lists(a, s);
+}
+
+/* The chunks of one length class of an overlapped call (flacmi_host.cpp): their batch kernels
+ * back to back, no list launch, retry kernel or memset between them, then one list pass and one
+ * retry pass over what all of them listed.  cls: the class's arguments (its first unit's
+ * pointers, its count); chunk: one chunk's, list_off its first unit counted from the class's.
+ * Only the pre-test build lists class-relative ids, so only calls that launch it qualify. */
+bool stream_class_ok(const ResidArgs& cls, int path, int residual_bytes) {
+    return stream_shape_ok(cls, path, residual_bytes) && cls.mode == FLACMI_MODE_REFERENCE && cls.prune && cls.energy != 0 &&
+           cls.bound && cls.chunk_weight;
+}
+hipError_t launch_stream_class_begin(const ResidArgs& cls, hipStream_t s) { /* the counters, once */
+    hipError_t e = hipMemsetAsync(cls.retry_sub, 0, 64 * 16 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    return hipMemsetAsync(cls.retry2_count, 0, sizeof(unsigned long long), s);
+}
+hipError_t launch_stream_class_batch(const ResidArgs& chunk, int64_t list_off, int64_t class_count, hipStream_t s) {
+    if (chunk.count <= 0) return hipSuccess;
+    ResidArgs a = chunk;
+    a.list_off = list_off;
+    a.retry_sub_cap = (class_count + 63) / 64; /* sub-list id & 63 of class-relative ids */
+    if (hipError_t e = launch_poison_lds(s); e != hipSuccess) return e;
+    return launch_stream_G(a, false, s);
+}
+hipError_t launch_stream_class_lists(const ResidArgs& cls, hipStream_t s) {
+    ResidArgs a = cls;
+    a.list_off = 0;
+    a.retry_sub_cap = (cls.count + 63) / 64;
+    return launch_stream_lists(a, s);
 }
 
 }  // namespace flacmi
