@@ -7,7 +7,7 @@ batches over several GPUs.
 
     python -m flac_amd encode infile.wav outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
                                                        [--correct-reader] [--fixed-only] [--fallback] [--stereo]
-                                                       [--lpc-sign]
+                                                       [--lpc-sign] [--wasted-bits] [--rice-search]
                                                        [--device N | --devices N,M,...]
 
     python -m flac_amd decode infile.flac outfile.wav [--device N] [--check-crc]
@@ -67,6 +67,9 @@ def make_argument_parser():
     enc.add_argument("--wasted-bits", action="store_true",
                      help="wasted-bits subframes: a block whose samples share w zero low bits (16-bit audio in a "
                           "24-bit file) is written at w bits less a sample; read back with decode --spec-wasted-bits")
+    enc.add_argument("--rice-search", action="store_true",
+                     help="exact Rice search: every partition takes the parameter that makes it smallest (the "
+                          "reference's floor(log2(mean)) has no value for a stretch of digital silence)")
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
@@ -148,7 +151,8 @@ def cmd_encode(args) -> None:
     with args.outfile.open("wb") as f:
         for bs in encode_wav(args.infile, parameters, quirk=not args.correct_reader, device=args.device,
                              devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback,
-                             stereo=args.stereo, lpc_sign=args.lpc_sign, wasted=args.wasted_bits):
+                             stereo=args.stereo, lpc_sign=args.lpc_sign, wasted=args.wasted_bits,
+                             rice_search=args.rice_search):
             f.write(bs)
     print(f"Encoding completed in {timer() - t0:.6g} seconds")
 

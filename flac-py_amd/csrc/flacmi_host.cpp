@@ -216,7 +216,8 @@ struct KnobDef {
     int dflt;
 };
 constexpr KnobDef kKnobs[kKnobCount] = {{"FLACMI_OVERLAP", -1}, {"FLACMI_MF8_GRID", 0}, {"FLACMI_STREAM_GENERIC", 0}, {"FLACMI_DECODE_GENERIC", 0},
-                                        {"FLACMI_PACK_GENERIC", 0}, {"FLACMI_DECODE_LPC", 1}, {"FLACMI_ENERGY_BOUND", 1}, {"FLACMI_INFO_GRID", 0}};
+                                        {"FLACMI_PACK_GENERIC", 0}, {"FLACMI_DECODE_LPC", 1}, {"FLACMI_ENERGY_BOUND", 1}, {"FLACMI_INFO_GRID", 0},
+                                        {"FLACMI_RICE_GRID", 0}};
 std::atomic<int> g_knob[kKnobCount];
 std::once_flag g_knob_once;
 void knobs_init() {
@@ -428,6 +429,10 @@ static int validate(const flacmi_batch* b, const flacmi_params* p, const flacmi_
         return fail(FLACMI_E_INVALID, "LPC_ONLY needs max_lpc_order >= 1");
     if ((p->reserved[1] & FLACMI_FLAG_LPC_SIGN) && (p->mode == FLACMI_MODE_FIXED_ONLY || p->mode == FLACMI_MODE_RICE_ONLY))
         return fail(FLACMI_E_INVALID, "FLACMI_FLAG_LPC_SIGN needs FLACMI_MODE_REFERENCE or FLACMI_MODE_LPC_ONLY");
+    if ((p->reserved[1] & FLACMI_FLAG_RICE_SEARCH) && p->mode == FLACMI_MODE_LPC_ONLY)
+        return fail(FLACMI_E_INVALID, "FLACMI_FLAG_RICE_SEARCH: FLACMI_MODE_LPC_ONLY has no Rice step");
+    if ((p->reserved[1] & FLACMI_FLAG_RICE_SEARCH) && p->rice_max > 8)
+        return fail(FLACMI_E_INVALID, "FLACMI_FLAG_RICE_SEARCH needs rice_max <= 8 (the FLAC subset bound)");
     if (p->mode != FLACMI_MODE_FIXED_ONLY && p->mode != FLACMI_MODE_RICE_ONLY && b->sample_bits + p->qlp_precision > 44)
         return fail(FLACMI_E_UNSUPPORTED,
                     "sample_bits + qlp_precision > 44: candidate residual sums may exceed int64 (see DESIGN.md)");
@@ -755,6 +760,24 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         }
         HIP_TRY(hipEventRecord(ev[1], s));
         for (int i = 0; i < nch; ++i) HIP_TRY(launch_resid_chunk(ch[i], s));
+    }
+    if (p->reserved[1] & FLACMI_FLAG_RICE_SEARCH) {
+        /* behind the last k_resid launch (list and retry passes included): every unit has its final status */
+        RiceArgs ra{};
+        ra.meta = o->meta;
+        ra.rice_params = o->rice_params;
+        ra.params_stride = o->params_stride;
+        ra.residual = o->residual;
+        ra.residual_stride = o->residual_stride;
+        ra.n_units = b->n_units;
+        ra.n_tail_units = b->n_tail_units;
+        ra.block_len = b->block_len;
+        ra.tail_len = b->n_tail_units ? b->tail_len : b->block_len;
+        ra.rmin = p->rice_min;
+        ra.rmax = p->rice_max;
+        ra.mode = p->mode;
+        ra.rice_order = p->mode == FLACMI_MODE_RICE_ONLY ? p->reserved[0] : 0;
+        if (debug_stop() == 0) HIP_TRY(launch_rice_search(ra, o->residual_bytes, knob(kKnobRiceGrid), s));
     }
     HIP_TRY(hipEventRecord(ev[2], s));
     ctx->ncalls++;

@@ -270,7 +270,7 @@ ResidLaunch resid_launch_config(int n, int rmax_eff, int residual_bytes);
 constexpr int kMaxFinestParts = 4096;
 
 /* flacmi_set_knob's knobs: the environment's value (read once) or the last value set */
-enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobEnergyBound, kKnobInfoGrid, kKnobCount };
+enum Knob { kKnobOverlap = 0, kKnobMf8Grid, kKnobStreamGeneric, kKnobDecodeGeneric, kKnobPackGeneric, kKnobDecodeLpc, kKnobEnergyBound, kKnobInfoGrid, kKnobRiceGrid, kKnobCount };
 int knob(Knob k);
 
 hipError_t launch_lpc(const LpcArgs& a, hipStream_t s);
@@ -315,6 +315,26 @@ hipError_t launch_stereo_rows(const void* lr, int32_t sample_bytes, int64_t lr_s
 hipError_t launch_wasted_rows(const void* in, int32_t sample_bytes, int64_t in_stride, int64_t n_units,
                               int32_t block_len, int32_t tail_len, int64_t n_tail_units, int32_t sample_bits,
                               void* out, int64_t out_stride, int32_t* wasted, hipStream_t s);
+/* The exact Rice search (k_rice.hip, FLACMI_FLAG_RICE_SEARCH): one launch over every unit of an
+ * analysis call, behind its last k_resid launch.  Units whose status is 0, or the reference's
+ * ValueError at FLACMI_SITE_RICE_LOG_DOMAIN / FLACMI_SITE_RICE_NEG_SHIFT (which then become status 0),
+ * get part_order, n_parts, coding_method, rice_bits, res_offset, res_len and rice_params[0 .. n_parts)
+ * by the rule in include/flacmi.h; nothing else is written.  rmax <= 8. */
+struct RiceArgs {
+    flacmi_unit_meta* meta;  /* [n_units] */
+    int32_t* rice_params;    /* [n_units][params_stride] */
+    int64_t params_stride;
+    const void* residual;    /* [n_units][residual_stride] u32 or u64 zig-zag rows, 16-byte aligned */
+    int64_t residual_stride;
+    int64_t n_units, n_tail_units;
+    int32_t block_len, tail_len;
+    int32_t rmin, rmax;
+    int32_t mode;            /* FLACMI_MODE_RICE_ONLY: a rescued unit's predictor order is rice_order */
+    int32_t rice_order;
+    int32_t pitch;           /* set by the launcher: partitions the LDS tables are laid out for, 2^rmax */
+};
+/* grid_cap: workgroups at most, 0 = the default */
+hipError_t launch_rice_search(const RiceArgs& a, int residual_bytes, int grid_cap, hipStream_t s);
 /* a.choice[f] from the four candidates' sizes (after k_sub_kinds in the fallback mode) */
 hipError_t launch_stereo_choose(const FrameArgs& a, hipStream_t s);
 

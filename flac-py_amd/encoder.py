@@ -187,7 +187,7 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
            samples: Iterator[list], parameters: EncoderParameters, *, device: int = 0,
            devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 2048,
            fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
-           lpc_sign: bool = False, wasted: bool = False) -> Iterator[bytes]:
+           lpc_sign: bool = False, wasted: bool = False, rice_search: bool = False) -> Iterator[bytes]:
     """flac/encoder.py:48-165 on the GPU: the per-channel analysis (k_lpc, k_resid) and
     the frame writer (k_frame.hip: Rice packing, headers, CRC-8/16), streamed through
     flacmi_encode_pipeline.  Only the stream header (magic + STREAMINFO) is written here.
@@ -213,14 +213,20 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
     as x >> w at sample_size - w bits behind a subframe header that declares w (include/flacmi.h
     FLACMI_FRAME_WASTED); it composes with fallback, fixed_only, lpc_sign and devices, with
     stereo=True it raises ValueError, and STREAMINFO is unchanged.  Such a stream is read with
-    decode(..., spec_wasted_bits=True); the reference's decoder misreads it."""
+    decode(..., spec_wasted_bits=True); the reference's decoder misreads it.  rice_search=True:
+    every Rice partition takes the parameter that makes it smallest and the unit the partition order
+    and coding method that make the residual smallest (include/flacmi.h FLACMI_FLAG_RICE_SEARCH, in
+    place of find_rice_parameter's floor(log2(mean)), encoder.py:730-753), so a partition of mean
+    below 1 (a stretch of digital silence) no longer raises ValueError; it composes with every other
+    option and needs rice_partition_order.stop <= 9."""
     _check_lpc_sign(lpc_sign, fixed_only)
+    _check_rice_search(rice_search, parameters)
     _check_stereo(stereo, channels)
     _check_wasted(wasted, stereo)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, frames, parameters)
-    params = _params(parameters, fixed_only, lpc_sign)
+    params = _params(parameters, fixed_only, lpc_sign, rice_search)
     n = parameters.block_size
 
     def batches():
@@ -242,7 +248,8 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
 def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameters: EncoderParameters, *,
                   frames: Optional[int] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
                   blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False,
-                  stereo: bool = False, lpc_sign: bool = False, wasted: bool = False) -> Iterator[bytes]:
+                  stereo: bool = False, lpc_sign: bool = False, wasted: bool = False,
+                  rice_search: bool = False) -> Iterator[bytes]:
     """encode() over planar PCM (int [channels][frames], e.g. from ingest.read_wav): the
     same bytes as encode(sample_rate, sample_size, channels, frames, <the frames of pcm>,
     parameters), without building a Python list per frame.  Blocks are cut straight into
@@ -251,13 +258,14 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
     from .ingest import planar_blocks
     channels, total = pcm.shape
     _check_lpc_sign(lpc_sign, fixed_only)
+    _check_rice_search(rice_search, parameters)
     _check_stereo(stereo, channels)
     _check_wasted(wasted, stereo)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, total if frames is None else frames,
                               parameters)
-    params = _params(parameters, fixed_only, lpc_sign)
+    params = _params(parameters, fixed_only, lpc_sign, rice_search)
     n = parameters.block_size
     nb = (total + n - 1) // n
     bpb = blocks_per_batch or _default_blocks(n, channels)
@@ -273,7 +281,7 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
 def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, device: int = 0,
                devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 0,
                fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
-               lpc_sign: bool = False, wasted: bool = False) -> Iterator[bytes]:
+               lpc_sign: bool = False, wasted: bool = False, rice_search: bool = False) -> Iterator[bytes]:
     """The reference CLI's encode action (flac/__main__.py:58-109) on a WAV file, streamed:
     the stream header first, then frames batch by batch (ingest.iter_wav_pcm), so the host
     holds a bounded number of batches of PCM.  A reader failure (the reference's IndexError
@@ -281,13 +289,14 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
     of the batches before it, as the reference CLI has written them by then."""
     from .ingest import iter_wav_pcm, planar_blocks, wav_info
     _check_lpc_sign(lpc_sign, fixed_only)
+    _check_rice_search(rice_search, parameters)
     info = wav_info(path)
     _check_stereo(stereo, info.channels)
     _check_wasted(wasted, stereo)
     if info.sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(info.sample_rate, info.sample_width * 8, info.channels, info.frames, parameters)
-    params = _params(parameters, fixed_only, lpc_sign)
+    params = _params(parameters, fixed_only, lpc_sign, rice_search)
     n, C = parameters.block_size, info.channels
     bpb = blocks_per_batch or _default_blocks(n, C)
 
@@ -304,6 +313,12 @@ def _check_lpc_sign(lpc_sign: bool, fixed_only: bool) -> None:
     """lpc_sign=True has no meaning without LPC candidates; refused before any device work."""
     if lpc_sign and fixed_only:
         raise ValueError("lpc_sign corrects the LPC candidates, fixed_only has none")
+
+
+def _check_rice_search(rice_search: bool, parameters: EncoderParameters) -> None:
+    """rice_search=True needs rice_partition_order.stop <= 9; refused before any device work."""
+    if rice_search and _rice_range(parameters.rice_partition_order)[1] > 8:
+        raise ValueError("rice_search needs rice_partition_order.stop <= 9 (the FLAC subset bound)")
 
 
 def _check_stereo(stereo: bool, channels: int) -> None:
@@ -328,11 +343,12 @@ def _stream_header(sample_rate, sample_size, channels, frames, parameters):
         sample_size=sample_size, samples=frames, md5=bytes(16))).buffer
 
 
-def _params(parameters: EncoderParameters, fixed_only: bool, lpc_sign: bool = False) -> abi.Params:
+def _params(parameters: EncoderParameters, fixed_only: bool, lpc_sign: bool = False,
+            rice_search: bool = False) -> abi.Params:
     rmin, rmax = _rice_range(parameters.rice_partition_order)
     mode = abi.MODE_FIXED_ONLY if fixed_only else abi.MODE_REFERENCE
     return make_params(parameters.lpc_order.stop - 1, parameters.qlp_precision, rmin, rmax, mode,
-                       lpc_sign=lpc_sign)
+                       lpc_sign=lpc_sign, rice_search=rice_search)
 
 
 # ---------------------------------------------------------------------------------
@@ -536,13 +552,16 @@ def encode_subframe_lpc(samples: list, lpc_order: range, precision: int, *, lpc_
 
 
 def encode_residual(samples: list, block_size: int, sample_size: int, predictor_order: int,
-                    partition_order_range: range) -> Residual:
-    """flac/encoder.py:632-652 on a residual list of block_size - predictor_order values."""
+                    partition_order_range: range, *, rice_search: bool = False) -> Residual:
+    """flac/encoder.py:632-652 on a residual list of block_size - predictor_order values.
+    rice_search=True: with the exact Rice search (FLACMI_FLAG_RICE_SEARCH)."""
     if len(samples) != block_size - predictor_order:
         raise NotImplementedError("residual length must be block_size - predictor_order")
     rmin, rmax = _rice_range(partition_order_range)
     row = [0] * predictor_order + list(samples)
-    p = make_params(0, 5, rmin, rmax, abi.MODE_RICE_ONLY)
+    if rice_search and rmax > 8:
+        raise ValueError("rice_search needs partition_order_range.stop <= 9 (the FLAC subset bound)")
+    p = make_params(0, 5, rmin, rmax, abi.MODE_RICE_ONLY, rice_search=rice_search)
     p.reserved[0] = predictor_order
     out, m = _one(row, p)
     _raise_for(m)

@@ -55,7 +55,8 @@ extern "C" {
       the same version (no struct changes size): flacmi_wasted_rows_device, FLACMI_FRAME_WASTED in
       flacmi_frame_params.reserved0, and flacmi_decode_params.reserved0 carries the decode flags
       (FLACMI_DECODE_WASTED_SPEC); a value with unknown bits is refused, callers that passed 0 there
-      see no change */
+      see no change; FLACMI_FLAG_RICE_SEARCH in flacmi_params.reserved[1] (callers never set bit 8
+      there and see no change) */
 #define FLACMI_ABI_VERSION 6
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
@@ -156,6 +157,40 @@ enum flacmi_flags {
      * k_resid_stream's list kernel takes, as with FLACMI_FLAG_ALL_CANDIDATES).  The reference decoder and
      * flacmi_decode_* read the LPC subframes it writes as they are. */
     FLACMI_FLAG_LPC_SIGN = 4,
+    /* the exact Rice search (off by default; with it clear every byte, status, field and launch is as
+     * without it).  The reference's find_rice_parameter (encoder.py:730-753) takes
+     * floor(log2(sum / len)): no value when a partition's zig-zag sum is 0 (FLACMI_SITE_RICE_LOG_DOMAIN),
+     * negative when the mean is below 1 (FLACMI_SITE_RICE_NEG_SHIFT), 31 (the 5-bit escape code) for a
+     * mean >= 2^31 (the TODO at encoder.py:751), and not the minimum; rice_partitions evaluates every
+     * candidate order before it chooses, so one near-silent stretch of n >> rice_max samples fails the
+     * unit.  The mode replaces the estimate with the parameter that makes each partition smallest.
+     * For a unit of n samples whose zig-zag residual is z = row[P .. n) (P = meta.res_offset where the
+     * analysis succeeded, meta.order on a rescued unit, params.reserved[0] in FLACMI_MODE_RICE_ONLY):
+     *   candidate orders  o in [rice_min, rice_max] with n % 2^o == 0 and (n >> o) > P
+     *                     (encoder.py:664-667); with none the unit keeps FLACMI_SITE_RICE_NO_ORDER
+     *   partitions        partition 0 has (n >> o) - P values, the others n >> o
+     *                     (split_samples_in_partitions)
+     *   partition cost    c_p(k) = sum_i (z_i >> k) + (1 + k) len_p  (sum of rice_size, encoder.py:756-760);
+     *                     c4_p = min over k in 0..14, c5_p = min over k in 0..30, the parameter being
+     *                     the smallest k that reaches the minimum
+     *   written bits      W4(o) = sum_p (4 + c4_p), W5(o) = sum_p (5 + c5_p)
+     *   walk              o ascending, method 4 before method 5: the first strictly smallest W wins.
+     *                     So coding_method == 5 iff some parameter exceeds 14 (the invariant of
+     *                     encode_residual, encoder.py:648-650), and no parameter exceeds 30.
+     * Written: meta.part_order, n_parts, coding_method, res_offset = P, res_len = n - P,
+     * rice_params[0 .. n_parts) and meta.rice_bits in the reference's estimate convention (W + 4 n_parts
+     * for method 4, W + 3 n_parts + #{k_p > 14} for method 5: the frame writer's size of the residual
+     * is W); nothing else of the record, no residual element, no rice_params word at or past n_parts.
+     * Units: those whose status is 0, and those whose status is FLACMI_STATUS_VALUE_ERROR at
+     * FLACMI_SITE_RICE_LOG_DOMAIN or FLACMI_SITE_RICE_NEG_SHIFT, which become status 0, site 0 (the
+     * analysis has written their residual row and their kind, order, shift and coefs); every other
+     * status is left alone (FLACMI_STATUS_RESIDUAL_WIDE: the caller's redo on 8-byte rows carries the
+     * flag).  It is an analysis flag: every entry point that takes flacmi_params honours it in
+     * FLACMI_MODE_REFERENCE, FIXED_ONLY and RICE_ONLY (the stereo mode's candidates and the wasted
+     * mode's shifted units included); with FLACMI_MODE_LPC_ONLY, which has no Rice step, or with
+     * rice_max > 8 (the FLAC subset bound) the call fails with FLACMI_E_INVALID before any launch.
+     * One more kernel (k_rice_search) runs behind the analysis kernels. */
+    FLACMI_FLAG_RICE_SEARCH = 8,
 };
 
 /* meta.lpc_order and meta.lpc_sum of a unit whose LPC candidates were pruned: exact lower
