@@ -199,7 +199,7 @@ DSITE = {name: 32 + i for i, name in enumerate((
     "sync", "block_size_code", "sample_rate_code", "channels_code", "sample_size_code", "reserved",
     "subframe_pad", "subframe_type", "lpc_precision", "coding_method", "partitions", "escape_zero",
     "neg_shift", "padding", "eof", "crc8", "crc16", "frame_end", "frame_number", "block_size", "channels",
-    "samples", "pcm_range"))}
+    "samples", "pcm_range", "side_range"))}
 DSITE_NAMES = {v: k for k, v in DSITE.items()}
 
 

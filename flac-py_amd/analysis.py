@@ -377,11 +377,13 @@ class Analyzer:
     def decode_frames(self, data: np.ndarray, offsets: np.ndarray, channels: int, sample_size: int,
                       first_frame: int = -1, expect: np.ndarray = None, block_len: int = 0, tail_len: int = 0,
                       n_tail_units: int = 0, out_stride: int = 0, check_crc: bool = True,
-                      spec_wasted_bits: bool = False):
+                      spec_wasted_bits: bool = False, samples_out: bool = True, frame_end: bool = False):
         """Host bytes in -> (decoded int32 rows [n_frames*channels][out_stride], frame status,
         mismatches per frame), decoded on the device.  `expect` (int16/int32 rows of the
         source units) turns on the in-kernel comparison.  spec_wasted_bits:
-        FLACMI_DECODE_WASTED_SPEC."""
+        FLACMI_DECODE_WASTED_SPEC.  samples_out=False passes no rows to the device (the builds
+        that only compare; the rows returned stay zero).  frame_end=True goes through
+        flacmi_decode_frames_end_device and returns the frame ends as a fourth array."""
         import torch
         dev = torch.device("cuda", self.device)
         n_frames = len(offsets) - 1
@@ -404,10 +406,19 @@ class Analyzer:
             eb = device_batch(e.data_ptr(), e.element_size(), 16 if e.element_size() == 2 else 32, e.shape[1],
                               e.shape[0], block_len, tail_len, n_tail_units)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        self.decode_frames_device(buf.data_ptr(), nb, off.data_ptr(), n_frames, dp, eb, out.data_ptr(), out_stride,
-                                  st.data_ptr(), mm.data_ptr(), stream)
+        out_ptr = out.data_ptr() if samples_out else 0
+        if frame_end:
+            fe = torch.full((max(n_frames, 1),), -2, dtype=torch.int64, device=dev)
+            check(self.lib.flacmi_decode_frames_end_device(self.ctx, buf.data_ptr(), nb, off.data_ptr(), n_frames,
+                                                           C.byref(dp), C.byref(eb) if eb is not None else None,
+                                                           out_ptr or None, out_stride, st.data_ptr(), mm.data_ptr(),
+                                                           fe.data_ptr(), stream), "flacmi_decode_frames_end_device")
+        else:
+            self.decode_frames_device(buf.data_ptr(), nb, off.data_ptr(), n_frames, dp, eb, out_ptr, out_stride,
+                                      st.data_ptr(), mm.data_ptr(), stream)
         torch.cuda.synchronize(dev)
-        return out.cpu().numpy(), st.cpu().numpy()[:n_frames], mm.cpu().numpy()[:n_frames]
+        res = out.cpu().numpy(), st.cpu().numpy()[:n_frames], mm.cpu().numpy()[:n_frames]
+        return res + (fe.cpu().numpy()[:n_frames],) if frame_end else res
 
     def index_frames(self, data, first_byte: int = 0, capacity: int = 0, base_offset: int = 0):
         """Host bytes in -> (candidate table as a CANDIDATE_DTYPE array, the true count), from

@@ -10,9 +10,9 @@ enum : int32_t {
     DS_SYNC = FLACMI_DSITE_SYNC, DS_BS_CODE, DS_SR_CODE, DS_CH_CODE, DS_SS_CODE, DS_RESERVED,
     DS_SUB_PAD, DS_SUB_TYPE, DS_LPC_PREC, DS_CODING, DS_PARTS, DS_ESC_ZERO, DS_NEG_SHIFT,
     DS_PADDING, DS_EOF, DS_CRC8, DS_CRC16, DS_FRAME_END, DS_FRAME_NO, DS_BLOCK_SIZE, DS_CHANNELS,
-    DS_SAMPLES,
+    DS_SAMPLES, DS_PCM_RANGE, DS_SIDE_RANGE,
 };
-static_assert(DS_SAMPLES == FLACMI_DSITE_SAMPLES, "flacmi_decode_site order");
+static_assert(DS_SAMPLES == FLACMI_DSITE_SAMPLES && DS_SIDE_RANGE == FLACMI_DSITE_SIDE_RANGE, "flacmi_decode_site order");
 
 __device__ __forceinline__ int32_t dstat(int32_t site) {
     int32_t s;

@@ -174,7 +174,13 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
             if (a.wasted_spec) ++wasted; /* the format codes k as k - 1 zeros and a one */
         }
         const int w = ss + (dbit ? 1 : 0) - wasted; /* sample_size_ (decoder.py:276) */
-        if (w <= 0) { pfail(DS_ESC_ZERO); break; }
+        /* sint(w <= 0) raises; a FIXED subframe of order 0 reads no sample at that width, so the
+         * reference decodes it (with the flag the width is the format's, and must be positive) */
+        if (w <= 0 && (a.wasted_spec || t != 8)) { pfail(DS_ESC_ZERO); break; }
+        /* a side channel of a 32-bit stream is read at 33 bits: a sample outside int32 cannot be
+         * kept in the history ring (flacmi.h, above FLACMI_STATUS_EOF) */
+        const bool wide = ss + (dbit ? 1 : 0) > 32;
+        bool side_range = false;
         /* FLACMI_DECODE_WASTED_SPEC: a restored sample leaves the ring shifted back (the prediction
          * reads the ring as parsed); off: parsed, not applied (decode_subframe) */
         const int wsh = a.wasted_spec ? wasted : 0;
@@ -187,7 +193,11 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
         if (t == 0) {
             cval = g.sint(w);
         } else if (t >= 8) {
-            for (int k = 0; k < order; ++k) ring[k][lane] = (int32_t)g.sint(w); /* warm-up */
+            for (int k = 0; k < order; ++k) { /* warm-up */
+                const int64_t v = g.sint(w);
+                side_range |= wide && v != (int32_t)v;
+                ring[k][lane] = (int32_t)v;
+            }
             if (t >= 32) {
                 const int prec = g.uint(4);
                 if (prec == 15) { pfail(DS_LPC_PREC); break; }
@@ -249,6 +259,7 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
                 }
                 s = r + (acc >> shift);
             }
+            side_range |= wide && s != (int32_t)s;
             ring[i & 31][lane] = (int32_t)s;
             h3 = h2;
             h2 = h1;
@@ -298,6 +309,7 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
             if (g.pos() > end_bit) { fail(DS_EOF); break; }
         }
         if (is_ref_error(st)) break;
+        if (side_range) fail(DS_SIDE_RANGE);
     }
     int64_t fend = -1; /* a.frame_end: where the parse ended (known once the footer is read) */
     if (!is_ref_error(st) && nch > 0) {

@@ -152,7 +152,8 @@ __device__ void frame_info(const InfoArgs& a, const int64_t f, const uint16_t* c
                 if (a.wasted_spec) ++wasted; /* FLACMI_DECODE_WASTED_SPEC: k is coded as k - 1 zeros and a one */
             }
             const int w = ss + (dbit ? 1 : 0) - wasted; /* sample_size_ (decoder.py:273) */
-            if (w <= 0) return err(DS_ESC_ZERO);
+            /* sint(w <= 0) raises; FIXED order 0 reads no sample at that width (as decode_general) */
+            if (w <= 0 && (a.wasted_spec || t != 8)) return err(DS_ESC_ZERO);
             const int order = t >= 32 ? (t & 31) + 1 : t >= 8 ? (t & 7) : 0;
             int64_t cval = 0, rbits = 0;
             uint64_t asum = 0;

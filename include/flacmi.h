@@ -504,7 +504,15 @@ int flacmi_host_free(flacmi_ctx* ctx, void* ptr);
  * the reference on every valid frame, with two documented choices: an L_R frame holds
  * dp->channels subframes (encoder.py:95 writes L_R whatever the channel count, so the
  * reference decoder cannot read back its own mono or 3+ channel streams), and, as in
- * decode_subframe, wasted bits are parsed but not shifted back in.
+ * decode_subframe, wasted bits are parsed but not shifted back in.  A third concerns 32-bit
+ * streams with L_S / S_R / M_S stereo only: the side channel is read at 33 bits, the reference
+ * restores it with unbounded integers, the device keeps every subframe's history as int32.  A
+ * side-channel sample outside int32 therefore fails the frame with FLACMI_STATUS_VERIFY at
+ * FLACMI_DSITE_SIDE_RANGE (samples_out is then unspecified for the frame) instead of decoding
+ * it modulo 2^32; a 33-bit side channel whose samples all fit int32 decodes exactly.  (The
+ * encoder's stereo mode stops at 31 bits and never writes such a frame.)  Everywhere else the
+ * history is the reference's value modulo 2^32: frames whose subframe samples and predictions
+ * fit int32, all that a conforming stream of up to 32 bits holds, decode exactly.
  *
  * Wasted bits as the format codes them (FLACMI_DECODE_WASTED_SPEC in dp->reserved0, off by
  * default; with it off every sample, status and frame end is as above).  A subframe whose header
@@ -535,7 +543,8 @@ enum flacmi_decode_site {
     FLACMI_DSITE_LPC_PRECISION,      /* :302  assert precision != 0b1111 */
     FLACMI_DSITE_CODING_METHOD,      /* :394  ValueError: cannot read coding method */
     FLACMI_DSITE_PARTITIONS,         /* :363-364  assert block size / partition order */
-    FLACMI_DSITE_ESCAPE_ZERO,        /* binary.py:131 sint(0): ValueError negative shift count */
+    FLACMI_DSITE_ESCAPE_ZERO,        /* binary.py:131 sint(0): ValueError negative shift count (an escape width of 0; a sample
+                                      * read at a width ss - wasted <= 0, which FIXED order 0 never does) */
     FLACMI_DSITE_NEG_SHIFT,          /* :496-497  ValueError: negative LPC shift in _decode_prediction */
     FLACMI_DSITE_PADDING,            /* :126  assert frame padding == 0 */
     FLACMI_DSITE_EOF,                /* binary.py:40  EOFError: the stream ends inside the frame */
@@ -547,6 +556,7 @@ enum flacmi_decode_site {
     FLACMI_DSITE_CHANNELS,           /* verifier: header channel count != dp->channels */
     FLACMI_DSITE_SAMPLES,            /* verifier: decoded samples differ from `expect` */
     FLACMI_DSITE_PCM_RANGE,          /* __main__.py:46  to_bytes: a sample does not fit the PCM width (OverflowError) */
+    FLACMI_DSITE_SIDE_RANGE,         /* verifier: a 33-bit side-channel sample (32-bit L_S / S_R / M_S) outside int32 */
 };
 typedef struct flacmi_decode_params {
     int32_t channels;        /* subframes per frame (STREAMINFO channels), 1..8 */
@@ -684,8 +694,8 @@ int flacmi_host_chain_walk(const flacmi_frame_candidate* table, int64_t n_candid
  * chain's own offsets into rows of their own pitch; its status is final), the PCM kernel,
  * copy out.  dp->first_frame is not checked (the reference never checks frame numbers);
  * with dp->check_crc = 0, the reference's behaviour, no CRC finding can occur; with 1 a
- * finding stops the stream at that frame like an exception.  The verifier's two documented
- * choices hold (above FLACMI_STATUS_EOF).
+ * finding stops the stream at that frame like an exception, as FLACMI_DSITE_SIDE_RANGE does
+ * with either setting.  The verifier's documented choices hold (above FLACMI_STATUS_EOF).
  *
  * data[0 .. bytes) is the chunk, frames start at first_byte; final_chunk = 0 says more bytes
  * follow, so a frame the chunk cuts off ends the call with res->consumed at its start (the

@@ -6,7 +6,7 @@ Run ONLY in the build container, where the reference is readable:
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_decode_golden.py
 
 flac-py's encoder only ever writes FIXED / LPC subframes in independent-channel frames,
-so the frames here are assembled bit by bit by this script (its own writer, below) to
+so the frames here are assembled bit by bit (tests/frame_assembler.py, the tests' own writer) to
 cover everything the reference decoder reads: CONSTANT / VERBATIM subframes, wasted-bits
 flags, escaped and Rice5Bit partitions, L_S / S_R / M_S stereo, uncommon block sizes and
 sample rates, 1..7-byte coded numbers, 24- and 32-bit samples, LPC orders up to 32, and one
@@ -30,160 +30,11 @@ from flac import decoder as D  # noqa: E402  (the reference, imported read-only)
 from flac.binary import Get  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
-FIXED = ((), (1,), (2, -1), (3, -3, 1), (4, -6, 4, -1))
 
 
-class Bits:
-    """MSB-first bit writer (this script's own)."""
-
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def u(self, x, n):
-        assert 0 <= x < (1 << n) or n == 0
-        self.v, self.n = (self.v << n) | x, self.n + n
-
-    def s(self, x, n):
-        assert -(1 << (n - 1)) <= x < (1 << (n - 1))
-        self.u(x & ((1 << n) - 1), n)
-
-    def rice(self, x, p):
-        z = (x << 1) ^ (x >> 63) if x >= 0 else ((-x) << 1) - 1
-        self.u(0, z >> p)
-        self.u(1, 1)
-        self.u(z & ((1 << p) - 1), p)
-
-    def pad(self):
-        if self.n % 8:
-            self.u(0, 8 - self.n % 8)
-
-    def data(self):
-        assert self.n % 8 == 0
-        return self.v.to_bytes(self.n // 8, "big") if self.n else b""
-
-
-def crc8(bs):
-    c = 0
-    for b in bs:
-        c ^= b
-        for _ in range(8):
-            c = ((c << 1) ^ 0x07) & 0xFF if c & 0x80 else (c << 1) & 0xFF
-    return c
-
-
-def crc16(bs):
-    c = 0
-    for b in bs:
-        c ^= b << 8
-        for _ in range(8):
-            c = ((c << 1) ^ 0x8005) & 0xFFFF if c & 0x8000 else (c << 1) & 0xFFFF
-    return c
-
-
-def coded(x):
-    if x < 128:
-        return bytes([x])
-    n = 2
-    while x >= (1 << (5 * n + 1)):
-        n += 1
-    out = [(0x80 | (x >> (6 * i)) & 0x3F) for i in reversed(range(n - 1))]
-    return bytes([((0xFF << (8 - n)) & 0xFF) | (x >> (6 * (n - 1)))] + out)
-
-
-def header(bs_code, bs, sr_code=0, ch_code=0, ss_code=0, fno=0, sync=0x7FFC, reserved=0, sr_extra=None):
-    b = Bits()
-    b.u(sync, 15)
-    b.u(0, 1)
-    b.u(bs_code, 4)
-    b.u(sr_code, 4)
-    b.u(ch_code, 4)
-    b.u(ss_code, 3)
-    b.u(reserved, 1)
-    for byte in coded(fno):
-        b.u(byte, 8)
-    if bs_code == 6:
-        b.u(bs - 1, 8)
-    elif bs_code == 7:
-        b.u(bs - 1, 16)
-    if sr_code == 12:
-        b.u(sr_extra or 48, 8)
-    elif sr_code in (13, 14):
-        b.u(sr_extra or 4410, 16)
-    h = b.data()
-    return h + bytes([crc8(h)])
-
-
-def predict(x, coefs, shift, order):
-    return [x[i] - (sum(c * x[i - 1 - j] for j, c in enumerate(coefs)) >> shift) for i in range(order, len(x))]
-
-
-def residual_bits(b, r, bs, order, po, params, method=0, esc=None):
-    """Rice partitions of residual r (len bs - order); params per partition; esc: {k: bits}."""
-    b.u(method, 2)
-    b.u(po, 4)
-    plen = bs >> po
-    i = 0
-    pb = 5 if method else 4
-    for k in range(1 << po):
-        n = plen - order if k == 0 else plen
-        part = r[i:i + n]
-        i += n
-        if esc and k in esc:
-            b.u((1 << pb) - 1, pb)
-            b.u(esc[k], 5)
-            for x in part:
-                b.s(x, esc[k]) if esc[k] else None
-        else:
-            # the listed parameter is a lower bound: raised to the encoder's own choice
-            # floor(log2(mean zig-zag)) so no code gets a huge unary part
-            zz = [2 * v if v >= 0 else -2 * v - 1 for v in part]
-            mean = sum(zz) // max(len(zz), 1)
-            p = max(params[k], mean.bit_length() - 1 if mean >= 1 else 0)
-            assert p < (1 << pb) - 1
-            b.u(p, pb)
-            for x in part:
-                b.rice(x, p)
-
-
-def sub_fixed(b, x, order, ss, po, params, method=0, esc=None, wasted=0, pad=0):
-    b.u(pad, 1)
-    b.u(8 | order, 6)
-    if wasted:
-        b.u(1, 1)  # get_wasted_bits (decoder.py:346-355) returns the count of zeros that follow
-        b.u(0, wasted)
-        b.u(1, 1)
-    else:
-        b.u(0, 1)
-    w = ss - wasted
-    for v in x[:order]:
-        b.s(v, w)
-    residual_bits(b, predict(x, FIXED[order], 0, order), len(x), order, po, params, method, esc)
-
-
-def sub_lpc(b, x, coefs, prec, shift, ss, po, params, method=0, esc=None, prec_field=None, raw_resid=None):
-    order = len(coefs)
-    b.u(0, 1)
-    b.u(32 | (order - 1), 6)
-    b.u(0, 1)
-    for v in x[:order]:
-        b.s(v, ss)
-    b.u(prec - 1 if prec_field is None else prec_field, 4)
-    b.s(shift, 5)
-    for c in coefs:
-        b.s(c, prec)
-    r = raw_resid if raw_resid is not None else predict(x, coefs, shift, order)
-    residual_bits(b, r, len(x), order, po, params, method, esc)
-
-
-def frame(hdr, subs):
-    b = Bits()
-    for byte in hdr:
-        b.u(byte, 8)
-    for f in subs:
-        f(b)
-    b.pad()
-    d = b.data()
-    return d + crc16(d).to_bytes(2, "big")
+sys.path.insert(0, os.path.dirname(OUT))
+from frame_assembler import (FIXED, Bits, coded, crc8, crc16, frame, header, predict,  # noqa: E402,F401
+                             residual_bits, sub_fixed, sub_lpc)
 
 
 def signal(rng, n, bits, tones=2):

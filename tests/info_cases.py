@@ -7,6 +7,10 @@ reference's own account of the same inputs (tests/golden/make_info_golden.py).
                       each of the fallback / stereo / lpc-sign fixtures, and `many_frames`
                       (decode.json's valid one-channel 16-bit frames repeated behind a
                       STREAMINFO until there are 130: the reference checks no frame number)
+
+k_frame_info is also held, field by field, to the generated frames of tests/decode_fuzz_cases.py
+(tests/test_gpu_decode_fuzz.py; the reference's verdicts on them are tests/golden/decode_fuzz.json,
+made by tests/golden/make_decode_fuzz_golden.py); stream_header() below serves that test too.
 """
 import json
 import os

@@ -10,6 +10,10 @@
    over many dwords, the restart of a lane that read past its look-ahead, the speculative
    block's rollback, BitReader::rice's long-run loop) round-trip exactly, and a bit flipped
    inside such a code is caught alike by both decoders.
+Frames of other encoders with the features combined (mixed waves, every alignment, the source-row
+builds, mutated frames) are in tests/test_gpu_decode_fuzz.py, which borrows this module's
+fixture: a seeded generator (decode_fuzz_cases.py), a plain model (decode_model.py) and the
+reference's verdicts in tests/golden/decode_fuzz.json (make_decode_fuzz_golden.py).
 Every test runs three times: with k_decode_fx taking the frames it accepts (the default), with
 the FLACMI_DECODE_GENERIC knob sending every frame through the general k_decode, and with
 FLACMI_DECODE_LPC=0 (k_decode_fx without its LPC pass: LPC frames straight to k_decode).
