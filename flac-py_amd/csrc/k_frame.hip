@@ -142,6 +142,10 @@ __device__ int frame_header_st(int64_t fno, int bs, int chan, uint8_t* h) {
  * the reference (its best fixed residual is all zeros, so find_rice_parameter takes log2(0),
  * or the LPC path has raised before), so only units with a nonzero status are scanned; a unit
  * escaped for its size or for the precision assertion is VERBATIM without reading its row.
+ * With FLACMI_FLAG_RICE_SEARCH such a block has status 0: the search rescues its all-zero fixed
+ * residual at one bit a sample (parameter 0 in every partition, which no other residual costs).
+ * A unit that stays as analysed with exactly that many residual bits and more bits than a
+ * CONSTANT subframe is scanned too, and is CONSTANT when its samples are all equal.
  * ==================================================================================== */
 template <bool ST, bool WB = false> /* ST: over the stereo mode's 4 n_frames candidate units, the side units one bit
                                        wider; WB: the wasted-bits mode, a unit at its own width and header */
@@ -154,7 +158,7 @@ __device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
     const int wz = unit_wasted<WB>(a, u);
     const int ss = unit_bits_of<ST>(a, u, wz);
     const int st = m.status;
-    bool esc;
+    bool esc, zero = false;
     if (st != 0) {
         esc = st == FLACMI_STATUS_ZERO_DIVISION || st == FLACMI_STATUS_ASSERTION || st == FLACMI_STATUS_VALUE_ERROR ||
               st == FLACMI_STATUS_OVERFLOW;
@@ -167,9 +171,12 @@ __device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
             for (int k = lane; k < m.n_parts; k += 64) cnt += rp[k] > 14 ? 1 : 0;
             for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
         }
-        esc = (int64_t)sub_prefix_bits(m, ss, a.q, wz) + sub_residual_bits(m, cnt) > 8 + wz + (int64_t)n * ss;
+        const int64_t bits = (int64_t)sub_prefix_bits(m, ss, a.q, wz) + sub_residual_bits(m, cnt);
+        esc = bits > 8 + wz + (int64_t)n * ss;
+        zero = !esc && m.kind == FLACMI_KIND_FIXED && m.coding_method == 4 &&
+               sub_residual_bits(m, 0) == 4LL * m.n_parts + (n - m.order) && bits > 8 + wz + ss;
     }
-    if (!esc || st == 0) {
+    if (!zero && (!esc || st == 0)) {
         if (lane == 0) a.sub_kind[u] = esc ? FLACMI_SUB_VERBATIM : FLACMI_SUB_ANALYSED;
         return;
     }
@@ -195,7 +202,7 @@ __device__ __forceinline__ void sub_kinds(const FrameArgs& a) {
         }
     }
     const bool any_diff = __any(diff);
-    if (lane == 0) a.sub_kind[u] = any_diff ? FLACMI_SUB_VERBATIM : FLACMI_SUB_CONSTANT;
+    if (lane == 0) a.sub_kind[u] = !any_diff ? FLACMI_SUB_CONSTANT : zero ? FLACMI_SUB_ANALYSED : FLACMI_SUB_VERBATIM;
 }
 __global__ __launch_bounds__(256) void k_sub_kinds(FrameArgs a) { sub_kinds<false>(a); }
 __global__ __launch_bounds__(256) void k_sub_kinds_st(FrameArgs a) { sub_kinds<true>(a); }

@@ -305,7 +305,10 @@ int flacmi_analyze_host(flacmi_ctx* ctx, const flacmi_batch* batch,
  *   - its analysis status is a reference exception (ZeroDivisionError, AssertionError,
  *     ValueError, OverflowError), or
  *   - it is an LPC subframe and the writer's precision assertion (encoder.py:619) would raise, or
- *   - its status is 0 and its exact subframe size is strictly greater than 8 + n * ss bits.
+ *   - its status is 0 and its exact subframe size is strictly greater than 8 + n * ss bits, or
+ *   - its status is 0, its n samples are all equal and its exact subframe size is strictly greater
+ *     than 8 + ss bits (the reference fails every such block; with FLACMI_FLAG_RICE_SEARCH it is a
+ *     FIXED subframe whose all-zero residual costs one bit a sample).
  * An escaped unit whose n samples are all equal is written as CONSTANT (header 0 000000 0, the
  * value in ss bits: 8 + ss bits), any other as VERBATIM (header 0 000001 0, every sample in ss
  * bits, two's complement truncated as warm-up samples are: 8 + n * ss bits).  Not escaped, so
@@ -348,7 +351,8 @@ int flacmi_analyze_host(flacmi_ctx* ctx, const flacmi_batch* batch,
  * per-channel analysis never looks at the sample size).  Its subframe header is 0 tttttt 0 when
  * w == 0, as without the mode, and 0 tttttt 1, w - 1 zero bits and a one when w > 0 (8 + w bits);
  * warm-up, CONSTANT and VERBATIM samples are written at ss - w bits.  With FLACMI_FRAME_FALLBACK a
- * unit is escaped when its exact size exceeds its own VERBATIM size 8 + w + n (ss - w); CONSTANT
+ * unit is escaped when its exact size exceeds its own VERBATIM size 8 + w + n (ss - w), or, all
+ * samples equal, its own CONSTANT size 8 + w + (ss - w); CONSTANT
  * writes x_0 >> w; every other fallback rule is unchanged.  Every frame of such a batch goes
  * through the general writer.  It composes with FLACMI_FRAME_FALLBACK, FLACMI_MODE_FIXED_ONLY and
  * FLACMI_FLAG_LPC_SIGN; together with FLACMI_STEREO_BEST the call returns FLACMI_E_INVALID (a

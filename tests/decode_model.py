@@ -4,7 +4,9 @@ unbounded integers, written from the statement catalogue of include/flacmi.h
 the kernels are specified to: the statements in their order, the first failing statement
 decides, a read past the last byte is EOFError, a negative LPC shift is raised only after the
 whole frame has parsed, get_wasted_bits yields the count of zeros, wasted bits are not shifted
-back in, and an L_R frame holds `channels` subframes.
+back in, and an L_R frame holds `channels` subframes.  With spec_wasted_bits=True
+(FLACMI_DECODE_WASTED_SPEC) the wasted count is the count of zeros plus one, as the format codes
+it, and every sample of the subframe is shifted back by it.
 
     decode(data, channels, sample_size, offset=0) -> Decoded | Failed
 
@@ -112,7 +114,7 @@ def _check(x, domain):
     return x
 
 
-def _subframe(g, bs, width, frame_bit0, domain):
+def _subframe(g, bs, width, frame_bit0, domain, spec=False):
     """One subframe: (samples, record, negative_shift)."""
     sub0 = g.p
     if g.uint(1) != 0:
@@ -120,7 +122,7 @@ def _subframe(g, bs, width, frame_bit0, domain):
     t = g.uint(6)
     if not (t <= 1 or 8 <= t <= 12 or t >= 32):
         raise _Stop(AssertionError, "subframe_type")
-    wasted = g.unary() if g.uint(1) else 0
+    wasted = g.unary() + int(spec) if g.uint(1) else 0
     w = width - wasted
     order = (t & 31) + 1 if t >= 32 else (t & 7) if t >= 8 else 0
     rec = {"bit_offset": sub0 - frame_bit0, "type": TYPE_NAMES[0 if t == 0 else 1 if t == 1 else 2 if t < 32 else 3],
@@ -174,10 +176,12 @@ def _subframe(g, bs, width, frame_bit0, domain):
                 x.append(_check(r + (sum(c * x[i - 1 - j] for j, c in enumerate(coefs)) >> shift), None if neg else domain))
         rec["residual_bits"] = g.p - r0
     rec["bits"] = g.p - sub0
+    if spec and wasted:
+        x = [_check(v << wasted, None if neg else domain) for v in x]
     return x, rec, neg
 
 
-def decode(data, channels, sample_size, offset=0, domain=True):
+def decode(data, channels, sample_size, offset=0, domain=True, spec_wasted_bits=False):
     """Frame at data[offset:] of the stream `data` (its end is the stream's end).  domain=False
     keeps going where OutOfDomain would be raised for a sample (unbounded integers throughout)."""
     g = _Reader(data, 8 * offset)
@@ -235,7 +239,7 @@ def decode(data, channels, sample_size, offset=0, domain=True):
         subs, neg = [], False
         for c in range(nch):
             side = (ch_code == 8 and c == 1) or (ch_code == 9 and c == 0) or (ch_code == 10 and c == 1)
-            x, rec, n = _subframe(g, bs, ss + int(side), 8 * offset, domain)
+            x, rec, n = _subframe(g, bs, ss + int(side), 8 * offset, domain, spec_wasted_bits)
             subs.append(x)
             rep["subframes"].append(rec)
             rep["n_subframes"] += 1

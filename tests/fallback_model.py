@@ -7,7 +7,9 @@ A unit of n samples at stream sample size ss is escaped when its status is a ref
 exception (1..4), when it is an LPC subframe and precision - 1 == 0b1111 (the writer's
 assertion), or when its status is 0 and its exact subframe size, counted here by writing it,
 is strictly greater than 8 + n * ss.  An escaped unit is CONSTANT when its samples are all
-equal, else VERBATIM.  Status 16 (the residual does not fit 32 bits) is not escaped.
+equal, else VERBATIM.  Status 16 (the residual does not fit 32 bits) is not escaped.  A unit of
+status 0 whose samples are all equal (the Rice search has rescued its all-zero residual) is
+CONSTANT when its size is strictly greater than 8 + ss.
 """
 import numpy as np
 
@@ -41,7 +43,11 @@ def sub_kind(samples, out, u, n, ss, q) -> int:
     elif int(m["kind"]) == FW.KIND_LPC and (q - 1) & 15 == 15:
         escaped = True
     else:
-        escaped = subframe_bits(samples, out, u, n, ss, q) > 8 + n * ss
+        bits = subframe_bits(samples, out, u, n, ss, q)
+        escaped = bits > 8 + n * ss
+        x = np.asarray(samples[:n])
+        if not escaped and bits > 8 + ss and (x == x[0]).all():
+            return CONSTANT
     if not escaped:
         return ANALYSED
     x = np.asarray(samples[:n])

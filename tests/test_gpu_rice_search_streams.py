@@ -19,6 +19,7 @@ from flac_amd import abi, info
 from flac_amd import encoder as enc
 from flac_amd.analysis import Analyzer, make_params
 from flac_amd.decoder import decode
+from mode_matrix_model import _wasted_subframe
 
 pytestmark = pytest.mark.gpu
 GOLD = G.load("rice_search_streams.json")["cases"]
@@ -144,17 +145,6 @@ def test_stereo_candidates_are_searched(az, fallback):
     assert stream == bytes.fromhex(GOLD[name]["header"]) + b"".join(want)
     _, _, ch, _, dec = decode(stream, check_crc=True)
     assert np.array_equal(np.asarray(list(dec), dtype=np.int64).reshape(-1, ch).T, x)
-
-
-def _wasted_subframe(bits, samples, m, zz, prm, n, width, q, w):
-    """frame_writer.subframe at `width` bits behind a header that declares w wasted bits
-    (0 tttttt 1, w - 1 zeros and a one)."""
-    t = FW.Bits()
-    FW.subframe(t, samples, m, zz, prm, n, width, q)
-    rest = t.n - 8
-    bits.put((t.v >> rest) | (1 if w else 0), 8)
-    bits.put(1, w)
-    bits.put(t.v & ((1 << rest) - 1), rest)
 
 
 def test_wasted_units_are_searched(az):
