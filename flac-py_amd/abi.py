@@ -73,6 +73,7 @@ FLAG_ALL_CANDIDATES = 1  # params.reserved[1]: exact sums for every LPC candidat
 FLAG_TIERS_ONLY = 2  # params.reserved[1]: prune with the partial-sum tiers alone (diagnostic)
 FLAG_LPC_SIGN = 4  # params.reserved[1]: the corrected LPC predictor sign (negated Levinson coefficients)
 FLAG_RICE_SEARCH = 8  # params.reserved[1]: the exact Rice search (k_rice_search behind the analysis)
+FLAG_SIZE_CHOICE = 16  # params.reserved[1]: subframe choice by exact written size (k_size_choice; params.reserved[2]: written width)
 LPC_PRUNED = -1          # meta.lpc_order / lpc_sum of a unit whose LPC candidates were pruned
 FRAME_FALLBACK = 1       # flacmi_frame_params.reserved0 (flacmi_frame_flags): CONSTANT / VERBATIM fallback subframes
 SUB_ANALYSED, SUB_CONSTANT, SUB_VERBATIM = 0, 1, 2  # flacmi_sub_kind: sub_kind[u] of the fallback mode

@@ -18,14 +18,18 @@ from ._lib import FlacmiError, check, load
 
 def make_params(max_lpc_order: int, qlp_precision: int, rice_min: int, rice_max: int,
                 mode: int = abi.MODE_REFERENCE, all_candidates: bool = False,
-                tiers_only: bool = False, lpc_sign: bool = False, rice_search: bool = False) -> abi.Params:
+                tiers_only: bool = False, lpc_sign: bool = False, rice_search: bool = False,
+                size_choice: bool = False, sample_size: int = 0) -> abi.Params:
     """all_candidates: exact sum(|r|) for every LPC candidate (meta.lpc_order / lpc_sum always
     exact); by default a unit whose LPC candidates provably lose reports abi.LPC_PRUNED there.
     tiers_only (diagnostic): the int8-MFMA path prunes with its partial-sum tiers alone.
     lpc_sign: FLACMI_FLAG_LPC_SIGN, the corrected LPC predictor sign (MODE_REFERENCE and
     MODE_LPC_ONLY; never prunes).  rice_search: FLACMI_FLAG_RICE_SEARCH, the exact Rice search (every
     mode but MODE_LPC_ONLY, rice_max <= 8): each partition's smallest parameter, the smallest order and
-    coding method; units the reference's Rice step fails on (sites 12, 13) get status 0."""
+    coding method; units the reference's Rice step fails on (sites 12, 13) get status 0.
+    size_choice: FLACMI_FLAG_SIZE_CHOICE, the fixed order, the LPC order and the subframe type by exact
+    written size (MODE_REFERENCE and MODE_FIXED_ONLY, with rice_search); sample_size: the bits a
+    warm-up sample is written at (0: the batch's sample_bits)."""
     p = abi.Params()
     p.max_lpc_order = max_lpc_order
     p.qlp_precision = qlp_precision
@@ -33,7 +37,9 @@ def make_params(max_lpc_order: int, qlp_precision: int, rice_min: int, rice_max:
     p.rice_max = rice_max
     p.mode = mode
     p.reserved[1] = (abi.FLAG_ALL_CANDIDATES if all_candidates else 0) | (abi.FLAG_TIERS_ONLY if tiers_only else 0) | \
-                    (abi.FLAG_LPC_SIGN if lpc_sign else 0) | (abi.FLAG_RICE_SEARCH if rice_search else 0)
+                    (abi.FLAG_LPC_SIGN if lpc_sign else 0) | (abi.FLAG_RICE_SEARCH if rice_search else 0) | \
+                    (abi.FLAG_SIZE_CHOICE if size_choice else 0)
+    p.reserved[2] = sample_size
     return p
 
 

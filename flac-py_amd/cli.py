@@ -7,7 +7,7 @@ batches over several GPUs.
 
     python -m flac_amd encode infile.wav outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
                                                        [--correct-reader] [--fixed-only] [--fallback] [--stereo]
-                                                       [--lpc-sign] [--wasted-bits] [--rice-search]
+                                                       [--lpc-sign] [--wasted-bits] [--rice-search] [--size-choice]
                                                        [--device N | --devices N,M,...]
 
     python -m flac_amd decode infile.flac outfile.wav [--device N] [--check-crc]
@@ -70,6 +70,9 @@ def make_argument_parser():
     enc.add_argument("--rice-search", action="store_true",
                      help="exact Rice search: every partition takes the parameter that makes it smallest (the "
                           "reference's floor(log2(mean)) has no value for a stretch of digital silence)")
+    enc.add_argument("--size-choice", action="store_true",
+                     help="choose each subframe's predictor by the exact bits it takes to write and not by the "
+                          "magnitude of its residual (needs --rice-search)")
     enc.add_argument("--device", type=int, default=0)
     enc.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",")], default=None, metavar="N,M,...",
                      help="encode on these devices, batches round-robin (frames in block order)")
@@ -152,7 +155,7 @@ def cmd_encode(args) -> None:
         for bs in encode_wav(args.infile, parameters, quirk=not args.correct_reader, device=args.device,
                              devices=args.devices, fixed_only=args.fixed_only, fallback=args.fallback,
                              stereo=args.stereo, lpc_sign=args.lpc_sign, wasted=args.wasted_bits,
-                             rice_search=args.rice_search):
+                             rice_search=args.rice_search, size_choice=args.size_choice):
             f.write(bs)
     print(f"Encoding completed in {timer() - t0:.6g} seconds")
 

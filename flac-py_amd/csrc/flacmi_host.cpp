@@ -433,6 +433,18 @@ static int validate(const flacmi_batch* b, const flacmi_params* p, const flacmi_
         return fail(FLACMI_E_INVALID, "FLACMI_FLAG_RICE_SEARCH: FLACMI_MODE_LPC_ONLY has no Rice step");
     if ((p->reserved[1] & FLACMI_FLAG_RICE_SEARCH) && p->rice_max > 8)
         return fail(FLACMI_E_INVALID, "FLACMI_FLAG_RICE_SEARCH needs rice_max <= 8 (the FLAC subset bound)");
+    if (p->reserved[1] & FLACMI_FLAG_SIZE_CHOICE) {
+        if (!(p->reserved[1] & FLACMI_FLAG_RICE_SEARCH))
+            return fail(FLACMI_E_INVALID, "FLACMI_FLAG_SIZE_CHOICE needs FLACMI_FLAG_RICE_SEARCH (sizes are the exact search's)");
+        if (p->mode != FLACMI_MODE_REFERENCE && p->mode != FLACMI_MODE_FIXED_ONLY)
+            return fail(FLACMI_E_INVALID, "FLACMI_FLAG_SIZE_CHOICE needs FLACMI_MODE_REFERENCE or FLACMI_MODE_FIXED_ONLY");
+        if (p->reserved[2] < 0 || p->reserved[2] > 33)
+            return fail(FLACMI_E_INVALID, "FLACMI_FLAG_SIZE_CHOICE: the written sample width (reserved[2]) must be 0..33");
+        const int L = p->mode == FLACMI_MODE_REFERENCE ? p->max_lpc_order : 0;
+        const size_t lds = size_choice_lds(b->block_len, b->sample_bytes, FLACMI_LPC_REC_WORDS(L), p->rice_max);
+        if (lds > 160 * 1024)
+            return fail(FLACMI_E_UNSUPPORTED, "block of %d samples needs %zu bytes of LDS", b->block_len, lds);
+    }
     if (p->mode != FLACMI_MODE_FIXED_ONLY && p->mode != FLACMI_MODE_RICE_ONLY && b->sample_bits + p->qlp_precision > 44)
         return fail(FLACMI_E_UNSUPPORTED,
                     "sample_bits + qlp_precision > 44: candidate residual sums may exceed int64 (see DESIGN.md)");
@@ -553,7 +565,7 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
     /* the energy bound (k_lpc's words, k_resid_stream's pre-test): wherever the stream kernel may prune */
     const int energy = debug_stop() >= 11 ? 0 : knob(kKnobEnergyBound); /* (the tier ablations time the tiers) */
     const bool prune_call = p->mode == FLACMI_MODE_REFERENCE && !o->lpc_sums &&
-                            !(p->reserved[1] & (FLACMI_FLAG_ALL_CANDIDATES | FLACMI_FLAG_LPC_SIGN)) && prune_allowed();
+                            !(p->reserved[1] & (FLACMI_FLAG_ALL_CANDIDATES | FLACMI_FLAG_LPC_SIGN | FLACMI_FLAG_SIZE_CHOICE)) && prune_allowed();
     const bool ebound = energy != 0 && prune_call && L >= 1 && L <= 12 && b->sample_bytes == 2 && p->qlp_precision <= 16;
     if (ebound) {
         if (int rc = ensure_buf(ctx->bound, sizeof(uint32_t) * 2 * (size_t)(b->n_units > 0 ? b->n_units : 1))) return rc;
@@ -711,6 +723,9 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         side = enc_side(ctx);
         if (side == s) overlap = false;
     }
+    /* FLACMI_FLAG_SIZE_CHOICE: k_lpc, then k_size_choice alone writes every unit (no k_resid, no k_rice_search) */
+    const bool size_choice = (p->reserved[1] & FLACMI_FLAG_SIZE_CHOICE) != 0;
+    if (size_choice) overlap = false;
     ctx->nchunks[slot] = overlap ? nch : 0;
     HIP_TRY(hipEventRecord(ev[0], s));
     if (overlap) {
@@ -759,9 +774,34 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
             HIP_TRY(launch_lpc(a, s));
         }
         HIP_TRY(hipEventRecord(ev[1], s));
-        for (int i = 0; i < nch; ++i) HIP_TRY(launch_resid_chunk(ch[i], s));
+        for (int i = 0; i < nch && !size_choice; ++i) HIP_TRY(launch_resid_chunk(ch[i], s));
     }
-    if (p->reserved[1] & FLACMI_FLAG_RICE_SEARCH) {
+    if (size_choice) {
+        SizeArgs sa{};
+        sa.samples = b->samples;
+        sa.stride = b->unit_stride;
+        sa.sample_bytes = b->sample_bytes;
+        sa.block_len = b->block_len;
+        sa.tail_len = b->n_tail_units ? b->tail_len : b->block_len;
+        sa.n_units = b->n_units;
+        sa.n_tail_units = b->n_tail_units;
+        sa.L = L;
+        sa.q = p->qlp_precision;
+        sa.mode = p->mode;
+        sa.rmin = p->rice_min;
+        sa.rmax = p->rice_max;
+        sa.ss = p->reserved[2] ? p->reserved[2] : b->sample_bits;
+        sa.rec = lpc ? (const int32_t*)ctx->rec.p : nullptr;
+        sa.rec_words = rec_words;
+        sa.meta = o->meta;
+        sa.rice_params = o->rice_params;
+        sa.params_stride = o->params_stride;
+        sa.residual = o->residual;
+        sa.residual_stride = o->residual_stride;
+        sa.fixed_sums = o->fixed_sums;
+        sa.lpc_sums = o->lpc_sums;
+        if (debug_stop() == 0) HIP_TRY(launch_size_choice(sa, o->residual_bytes, knob(kKnobRiceGrid), s));
+    } else if (p->reserved[1] & FLACMI_FLAG_RICE_SEARCH) {
         /* behind the last k_resid launch (list and retry passes included): every unit has its final status */
         RiceArgs ra{};
         ra.meta = o->meta;
@@ -934,6 +974,20 @@ static int own_sub_kind(const flacmi_frame_params* fp, DevBuf& buf, FrameArgs& a
  * outputs hold 2 nu units, the sample buffer nu + F rows (the mid rows behind the caller's, same
  * pitch) and the side rows live in a buffer of their own (int32, their own pitch). */
 static bool stereo_on(const flacmi_frame_params* fp) { return fp->reserved[1] == FLACMI_STEREO_BEST; }
+
+/* FLACMI_FLAG_SIZE_CHOICE at the host entry points: the written width is the stream's (a copy of
+ * the parameters with reserved[2] filled, `out`); not with the wasted-bits mode, where it is per unit */
+static int size_choice_params(const flacmi_params* p, const flacmi_frame_params* fp, flacmi_params* out) {
+    *out = *p;
+    if (!(p->reserved[1] & FLACMI_FLAG_SIZE_CHOICE)) return 0;
+    if (fp->reserved0 & FLACMI_FRAME_WASTED)
+        return fail(FLACMI_E_INVALID, "FLACMI_FLAG_SIZE_CHOICE does not combine with FLACMI_FRAME_WASTED");
+    if (p->reserved[2] != 0 && p->reserved[2] != fp->sample_size)
+        return fail(FLACMI_E_INVALID, "FLACMI_FLAG_SIZE_CHOICE: reserved[2] = %d disagrees with sample_size %d",
+                    p->reserved[2], fp->sample_size);
+    out->reserved[2] = fp->sample_size;
+    return 0;
+}
 static size_t stereo_out_units(const flacmi_frame_params* fp, size_t nu) { return stereo_on(fp) ? 2 * nu : nu; }
 static size_t stereo_sample_rows(const flacmi_frame_params* fp, size_t nu) { return stereo_on(fp) ? nu + nu / 2 : nu; }
 static const void* stereo_mid(const flacmi_batch& db) {
@@ -970,7 +1024,12 @@ static int stereo_analyze(flacmi_ctx* ctx, const flacmi_batch& db, const flacmi_
     bs.unit_stride = side_stride;
     const flacmi_batch* batches[3] = {&db, &bm, &bs};
     const int64_t unit0[3] = {0, 2 * F, 3 * F};
+    /* FLACMI_FLAG_SIZE_CHOICE: the side rows are written one bit wider than the caller's and the mid rows */
+    flacmi_params side_params = *params;
+    if ((params->reserved[1] & FLACMI_FLAG_SIZE_CHOICE) && params->reserved[2]) side_params.reserved[2] += 1;
+    const flacmi_params* const caller_params = params;
     for (int i = 0; i < 3; ++i) {
+        params = i == 2 ? &side_params : caller_params;
         flacmi_outputs oi = o;
         oi.meta = o.meta + unit0[i];
         oi.rice_params = o.rice_params + unit0[i] * o.params_stride;
@@ -1825,6 +1884,9 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
     int64_t nf = 0;
     if (int rc = validate_frames(batch, fp, &nf)) return rc;
     if (!params || !frame_offsets || !frame_status) return fail(FLACMI_E_INVALID, "null argument");
+    flacmi_params sized;
+    if (int rc = size_choice_params(params, fp, &sized)) return rc;
+    params = &sized;
     ctx->frames_bytes = 0;
     if (nf == 0) {
         frame_offsets[0] = 0;
@@ -2112,6 +2174,9 @@ extern "C" int flacmi_encode_pipeline(flacmi_ctx* ctx, const flacmi_batch* batch
     if (int rc = validate_frames(batch, fp, &nf)) return rc;
     if (!params || !frame_offsets || !frame_status || (!out && out_capacity > 0))
         return fail(FLACMI_E_INVALID, "null argument");
+    flacmi_params sized;
+    if (int rc = size_choice_params(params, fp, &sized)) return rc;
+    params = &sized;
     const int C = fp->channels;
     if (units_per_batch < C || units_per_batch % C) return fail(FLACMI_E_INVALID, "units_per_batch must be a positive multiple of channels");
     if (batch->unit_stride < batch->block_len) return fail(FLACMI_E_INVALID, "unit_stride < block_len");

@@ -335,6 +335,35 @@ struct RiceArgs {
 };
 /* grid_cap: workgroups at most, 0 = the default */
 hipError_t launch_rice_search(const RiceArgs& a, int residual_bytes, int grid_cap, hipStream_t s);
+/* The subframe choice by exact written size (k_size.hip, FLACMI_FLAG_SIZE_CHOICE): one launch over
+ * every unit of an analysis call, behind k_lpc and in place of k_resid and k_rice_search.  Every
+ * unit's whole record, its rice_params and its zig-zag row are written by the rule in
+ * include/flacmi.h; a unit whose LPC record carries a status gets that status and site. */
+struct SizeArgs {
+    const void* samples;     /* int16 or int32 rows, 16-byte aligned */
+    int64_t stride;
+    int32_t sample_bytes;
+    int32_t block_len, tail_len;
+    int64_t n_units, n_tail_units;
+    int32_t L, q, mode;      /* FLACMI_MODE_REFERENCE or FLACMI_MODE_FIXED_ONLY */
+    int32_t rmin, rmax;      /* rmax <= 8 */
+    int32_t ss;              /* bits a warm-up sample of these units is written at */
+    const int32_t* rec;      /* [n_units][rec_words] k_lpc's records (NULL in fixed-only mode) */
+    int32_t rec_words;
+    flacmi_unit_meta* meta;  /* [n_units] */
+    int32_t* rice_params;    /* [n_units][params_stride] */
+    int64_t params_stride;
+    void* residual;          /* [n_units][residual_stride] u32 or u64, 16-byte aligned rows */
+    int64_t residual_stride;
+    int64_t* fixed_sums;     /* optional [n_units][5]: each fixed candidate's bits, -1 when not eligible */
+    int64_t* lpc_sums;       /* optional [n_units][32]: each LPC candidate's, 0 at and past L */
+    int32_t pitch;           /* set by the launcher: 2^rmax */
+};
+/* dynamic LDS of k_size_choice for a call (the Rice tables, the best parameters, the candidate's
+ * taps, the unit's record and its samples) */
+size_t size_choice_lds(int block_len, int sample_bytes, int rec_words, int rmax);
+/* grid_cap: workgroups at most, 0 = the default */
+hipError_t launch_size_choice(const SizeArgs& a, int residual_bytes, int grid_cap, hipStream_t s);
 /* a.choice[f] from the four candidates' sizes (after k_sub_kinds in the fallback mode) */
 hipError_t launch_stereo_choose(const FrameArgs& a, hipStream_t s);
 

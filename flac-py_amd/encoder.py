@@ -187,7 +187,8 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
            samples: Iterator[list], parameters: EncoderParameters, *, device: int = 0,
            devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 2048,
            fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
-           lpc_sign: bool = False, wasted: bool = False, rice_search: bool = False) -> Iterator[bytes]:
+           lpc_sign: bool = False, wasted: bool = False, rice_search: bool = False,
+           size_choice: bool = False) -> Iterator[bytes]:
     """flac/encoder.py:48-165 on the GPU: the per-channel analysis (k_lpc, k_resid) and
     the frame writer (k_frame.hip: Rice packing, headers, CRC-8/16), streamed through
     flacmi_encode_pipeline.  Only the stream header (magic + STREAMINFO) is written here.
@@ -218,15 +219,22 @@ def encode(sample_rate: int, sample_size: int, channels: int, frames: int,
     and coding method that make the residual smallest (include/flacmi.h FLACMI_FLAG_RICE_SEARCH, in
     place of find_rice_parameter's floor(log2(mean)), encoder.py:730-753), so a partition of mean
     below 1 (a stretch of digital silence) no longer raises ValueError; it composes with every other
-    option and needs rice_partition_order.stop <= 9."""
+    option and needs rice_partition_order.stop <= 9.  size_choice=True (with rice_search=True): the
+    fixed order, the LPC order and the subframe type are chosen by the exact number of bits each
+    candidate subframe takes (warm-up, coefficients and the searched residual) and not by
+    sum |residual| (include/flacmi.h FLACMI_FLAG_SIZE_CHOICE, in place of the min() at encoder.py:352
+    and :404 and the comparison at :135-157, whose tie no longer raises); it composes with fallback,
+    stereo, lpc_sign, fixed_only and devices; without rice_search, with wasted=True or with
+    rice_partition_order.stop > 9 it raises ValueError."""
     _check_lpc_sign(lpc_sign, fixed_only)
     _check_rice_search(rice_search, parameters)
+    _check_size_choice(size_choice, rice_search, wasted, parameters)
     _check_stereo(stereo, channels)
     _check_wasted(wasted, stereo)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, frames, parameters)
-    params = _params(parameters, fixed_only, lpc_sign, rice_search)
+    params = _params(parameters, fixed_only, lpc_sign, rice_search, size_choice)
     n = parameters.block_size
 
     def batches():
@@ -249,7 +257,7 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
                   frames: Optional[int] = None, device: int = 0, devices: Optional[Sequence[int]] = None,
                   blocks_per_batch: int = 0, fixed_only: bool = False, fallback: bool = False,
                   stereo: bool = False, lpc_sign: bool = False, wasted: bool = False,
-                  rice_search: bool = False) -> Iterator[bytes]:
+                  rice_search: bool = False, size_choice: bool = False) -> Iterator[bytes]:
     """encode() over planar PCM (int [channels][frames], e.g. from ingest.read_wav): the
     same bytes as encode(sample_rate, sample_size, channels, frames, <the frames of pcm>,
     parameters), without building a Python list per frame.  Blocks are cut straight into
@@ -259,13 +267,14 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
     channels, total = pcm.shape
     _check_lpc_sign(lpc_sign, fixed_only)
     _check_rice_search(rice_search, parameters)
+    _check_size_choice(size_choice, rice_search, wasted, parameters)
     _check_stereo(stereo, channels)
     _check_wasted(wasted, stereo)
     if sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(sample_rate, sample_size, channels, total if frames is None else frames,
                               parameters)
-    params = _params(parameters, fixed_only, lpc_sign, rice_search)
+    params = _params(parameters, fixed_only, lpc_sign, rice_search, size_choice)
     n = parameters.block_size
     nb = (total + n - 1) // n
     bpb = blocks_per_batch or _default_blocks(n, channels)
@@ -281,7 +290,8 @@ def encode_planar(sample_rate: int, sample_size: int, pcm: np.ndarray, parameter
 def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, device: int = 0,
                devices: Optional[Sequence[int]] = None, blocks_per_batch: int = 0,
                fixed_only: bool = False, fallback: bool = False, stereo: bool = False,
-               lpc_sign: bool = False, wasted: bool = False, rice_search: bool = False) -> Iterator[bytes]:
+               lpc_sign: bool = False, wasted: bool = False, rice_search: bool = False,
+               size_choice: bool = False) -> Iterator[bytes]:
     """The reference CLI's encode action (flac/__main__.py:58-109) on a WAV file, streamed:
     the stream header first, then frames batch by batch (ingest.iter_wav_pcm), so the host
     holds a bounded number of batches of PCM.  A reader failure (the reference's IndexError
@@ -290,13 +300,14 @@ def encode_wav(path, parameters: EncoderParameters, *, quirk: bool = True, devic
     from .ingest import iter_wav_pcm, planar_blocks, wav_info
     _check_lpc_sign(lpc_sign, fixed_only)
     _check_rice_search(rice_search, parameters)
+    _check_size_choice(size_choice, rice_search, wasted, parameters)
     info = wav_info(path)
     _check_stereo(stereo, info.channels)
     _check_wasted(wasted, stereo)
     if info.sample_rate <= 48_000:
         assert parameters.lpc_order.stop <= 13
     yield from _stream_header(info.sample_rate, info.sample_width * 8, info.channels, info.frames, parameters)
-    params = _params(parameters, fixed_only, lpc_sign, rice_search)
+    params = _params(parameters, fixed_only, lpc_sign, rice_search, size_choice)
     n, C = parameters.block_size, info.channels
     bpb = blocks_per_batch or _default_blocks(n, C)
 
@@ -319,6 +330,19 @@ def _check_rice_search(rice_search: bool, parameters: EncoderParameters) -> None
     """rice_search=True needs rice_partition_order.stop <= 9; refused before any device work."""
     if rice_search and _rice_range(parameters.rice_partition_order)[1] > 8:
         raise ValueError("rice_search needs rice_partition_order.stop <= 9 (the FLAC subset bound)")
+
+
+def _check_size_choice(size_choice: bool, rice_search: bool, wasted: bool, parameters: EncoderParameters) -> None:
+    """size_choice=True is defined over the exact Rice search and the stream's one sample width;
+    refused before any device work."""
+    if not size_choice:
+        return
+    if not rice_search:
+        raise ValueError("size_choice needs rice_search (candidate sizes are the exact search's)")
+    if wasted:
+        raise ValueError("size_choice and wasted bits do not combine yet")
+    if _rice_range(parameters.rice_partition_order)[1] > 8:
+        raise ValueError("size_choice needs rice_partition_order.stop <= 9 (the FLAC subset bound)")
 
 
 def _check_stereo(stereo: bool, channels: int) -> None:
@@ -344,11 +368,11 @@ def _stream_header(sample_rate, sample_size, channels, frames, parameters):
 
 
 def _params(parameters: EncoderParameters, fixed_only: bool, lpc_sign: bool = False,
-            rice_search: bool = False) -> abi.Params:
+            rice_search: bool = False, size_choice: bool = False) -> abi.Params:
     rmin, rmax = _rice_range(parameters.rice_partition_order)
     mode = abi.MODE_FIXED_ONLY if fixed_only else abi.MODE_REFERENCE
     return make_params(parameters.lpc_order.stop - 1, parameters.qlp_precision, rmin, rmax, mode,
-                       lpc_sign=lpc_sign, rice_search=rice_search)
+                       lpc_sign=lpc_sign, rice_search=rice_search, size_choice=size_choice)
 
 
 # ---------------------------------------------------------------------------------

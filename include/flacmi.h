@@ -56,7 +56,9 @@ extern "C" {
       flacmi_frame_params.reserved0, and flacmi_decode_params.reserved0 carries the decode flags
       (FLACMI_DECODE_WASTED_SPEC); a value with unknown bits is refused, callers that passed 0 there
       see no change; FLACMI_FLAG_RICE_SEARCH in flacmi_params.reserved[1] (callers never set bit 8
-      there and see no change) */
+      there and see no change); FLACMI_FLAG_SIZE_CHOICE in flacmi_params.reserved[1], with the written
+      sample width in flacmi_params.reserved[2] (callers never set bit 16 there, passed 0 in
+      reserved[2], and see no change) */
 #define FLACMI_ABI_VERSION 6
 #define FLACMI_MAX_LPC_ORDER 32      /* EncoderParameters: lpc_order.stop <= 33 (encoder.py:42) */
 #define FLACMI_MAX_BLOCK 65535       /* largest block the reference writes (encoder.py:249-253, 16-bit uncommon
@@ -133,7 +135,8 @@ typedef struct flacmi_params {
     int32_t rice_max;        /* rice_partition_order.stop - 1 (rice_max < rice_min: empty range) */
     int32_t mode;            /* flacmi_mode */
     int32_t reserved[3];     /* reserved[0]: predictor order in FLACMI_MODE_RICE_ONLY, else 0;
-                                reserved[1]: flacmi_flags; reserved[2]: 0 */
+                                reserved[1]: flacmi_flags; reserved[2]: with FLACMI_FLAG_SIZE_CHOICE the
+                                bits a warm-up sample is written at (0: batch.sample_bits), else 0 */
 } flacmi_params;
 
 /* params.reserved[1] bits */
@@ -191,6 +194,49 @@ enum flacmi_flags {
      * rice_max > 8 (the FLAC subset bound) the call fails with FLACMI_E_INVALID before any launch.
      * One more kernel (k_rice_search) runs behind the analysis kernels. */
     FLACMI_FLAG_RICE_SEARCH = 8,
+    /* the subframe choice by exact written size (off by default; with it clear every byte, status,
+     * field and launch is as without it).  The reference picks the fixed order (encoder.py:350-352),
+     * the LPC order (:398-404) and the subframe type (:135-157) by sum |r|, which ignores what an
+     * order costs; the TODO in encode() (:104-118) wants "a reliable way of determining the size of
+     * subframe structures".  The mode replaces those three statements and nothing else.  For a unit
+     * of n samples written at ss bits (ss = params.reserved[2], or batch.sample_bits when that is 0:
+     * batch.sample_bits only bounds the data, the stream may be wider):
+     *   candidates   in this order: the fixed orders 0..4 (order 0 alone when n <= 4, :334); in
+     *                FLACMI_MODE_REFERENCE then the LPC orders 1..L with the quantised coefficients
+     *                and shift of the analysis' record for that order (so FLACMI_FLAG_LPC_SIGN is
+     *                honoured as without the mode); FLACMI_MODE_FIXED_ONLY has the fixed ones only
+     *   eligible     a candidate of predictor order P with a partition order (some o in
+     *                [rice_min, rice_max] with n % 2^o == 0 and (n >> o) > P, :664-667) that, if LPC,
+     *                is not in the quantiser's negative-shift branch (the ([], 0) record, which the
+     *                reference writes undecodably) and has qlp_precision != 16 (the writer's
+     *                assertion, :619)
+     *   size         bits = 8 + P ss + (LPC: 9 + P qlp_precision) + 6 + W, with W the written residual
+     *                size of FLACMI_FLAG_RICE_SEARCH on the candidate's zig-zag residual (same walk,
+     *                same parameter ties): exact whatever the residual row width of the call
+     *   choice       the first strictly smallest bits in candidate order; no tie raises
+     *                (FLACMI_SITE_CHOICE_TIE never appears).  With no eligible candidate the unit has
+     *                FLACMI_STATUS_ASSERTION at FLACMI_SITE_RICE_NO_ORDER and, but for fixed_* / lpc_*,
+     *                a zero record.
+     * A unit whose LPC stage fails (the record's status: sites 1..9, FLACMI_SITE_LPC_EMPTY included)
+     * keeps that status and site and a zero record: encode_subframe_lpc raises before any choice.
+     * Every other unit has status 0, except that a chosen residual that does not fit 4-byte rows
+     * gives FLACMI_STATUS_RESIDUAL_WIDE as without the mode (kind, order, shift, coefs and fixed_* /
+     * lpc_* written; the caller's redo on 8-byte rows carries the flag).  Written: the whole record
+     * of the chosen candidate (kind, order, shift, ncoefs, coefs, res_offset = P, res_len = n - P,
+     * part_order, n_parts, coding_method, rice_bits in the estimate convention of
+     * FLACMI_FLAG_RICE_SEARCH), rice_params[0 .. n_parts) and the zig-zag residual row.
+     * fixed_order / lpc_order are the first smallest eligible candidate of each family and
+     * fixed_sum / lpc_sum its bits (-1 for both with no eligible candidate; lpc_* 0 in
+     * FLACMI_MODE_FIXED_ONLY); lpc_tiers is 0.  outputs.fixed_sums[u][k] and outputs.lpc_sums[u][j]
+     * hold every candidate's bits, -1 where it is not an eligible candidate (lpc_sums 0 at and past L).
+     * Needs FLACMI_FLAG_RICE_SEARCH (with its rice_max <= 8), FLACMI_MODE_REFERENCE or
+     * FLACMI_MODE_FIXED_ONLY and reserved[2] in 0..33; anything else fails with FLACMI_E_INVALID before any
+     * launch.  flacmi_encode_host / flacmi_encode_pipeline fill reserved[2] from
+     * flacmi_frame_params.sample_size when it is 0, refuse another value, pass ss + 1 for the stereo
+     * mode's side rows, and refuse the flag together with FLACMI_FRAME_WASTED (the written width is
+     * then per unit: a follow-up).  One kernel (k_size_choice) runs behind k_lpc in place of the
+     * residual kernels and k_rice_search. */
+    FLACMI_FLAG_SIZE_CHOICE = 16,
 };
 
 /* meta.lpc_order and meta.lpc_sum of a unit whose LPC candidates were pruned: exact lower
