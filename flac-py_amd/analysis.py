@@ -96,7 +96,10 @@ def get_knob(name: str) -> int:
 def set_knob(name: str, value: int) -> None:
     """Set a test/diagnostic knob (flacmi_set_knob): FLACMI_OVERLAP, FLACMI_MF8_GRID,
     FLACMI_STREAM_GENERIC, FLACMI_DECODE_GENERIC, FLACMI_ENERGY_BOUND, FLACMI_RICE_GRID.  The library reads their environment variables once; this is the
-    thread-safe way to change them afterwards."""
+    thread-safe way to change them afterwards.  FLACMI_ENERGY_BOUND (the stream kernel's pruning
+    calls): 0 the tiers alone; 1 (default) both pre-tests (the energy bound over every order, then
+    orders 2 .. L by it and order 1 by the closed form), then the tiers; 2 the first pre-test,
+    then the exact pass; 3 both, then the exact pass; 4 the first, then the tiers."""
     check(load().flacmi_set_knob(name.encode(), int(value)), "flacmi_set_knob")
 
 

@@ -162,7 +162,7 @@ struct flacmi_ctx {
     std::map<int, double*> windows;
     std::map<int, std::pair<int, int>> window_one; /* per n: [lo, hi) where the weight is 1.0 */
     std::map<int, uint16_t*> chunk_weights;        /* per n: the energy bound's weight per 8-sample chunk */
-    DevBuf bound;                                  /* k_lpc's energy-bound words [units][2] */
+    DevBuf bound;                                  /* k_lpc's bound words [units][kBoundWords] */
     DevBuf rec, retry, h_samples, h_meta, h_params, h_residual, h_acf, h_fs, h_ls, h_recs;
     uint16_t* d_crc = nullptr;  /* CRC-16 slice tables [4][256] + power tables [28][512] */
     DevBuf scan, h_offsets, h_status, h_frames, dec, slow;
@@ -568,7 +568,7 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
                             !(p->reserved[1] & (FLACMI_FLAG_ALL_CANDIDATES | FLACMI_FLAG_LPC_SIGN | FLACMI_FLAG_SIZE_CHOICE)) && prune_allowed();
     const bool ebound = energy != 0 && prune_call && L >= 1 && L <= 12 && b->sample_bytes == 2 && p->qlp_precision <= 16;
     if (ebound) {
-        if (int rc = ensure_buf(ctx->bound, sizeof(uint32_t) * 2 * (size_t)(b->n_units > 0 ? b->n_units : 1))) return rc;
+        if (int rc = ensure_buf(ctx->bound, sizeof(uint32_t) * kBoundWords * (size_t)(b->n_units > 0 ? b->n_units : 1))) return rc;
     }
     /* fast-kernel retry lists: 64 sub-list counters (k_resid_stream's batch kernel, 128 B apart),
      * a counter and one batch index per unit (plus 64 for the sub-lists' rounding), then the
@@ -646,7 +646,7 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         a.q = p->qlp_precision;
         a.lpc_sign = (p->reserved[1] & FLACMI_FLAG_LPC_SIGN) != 0;
         if (int rc = get_window(ctx, k.n, (double**)&a.window, &a.fuse_lo, &a.fuse_hi)) return rc;
-        a.bound = ebound ? (uint32_t*)ctx->bound.p + 2 * k.unit0 : nullptr;
+        a.bound = ebound ? (uint32_t*)ctx->bound.p + kBoundWords * k.unit0 : nullptr;
         if (b->sample_bits > 26) a.fuse_lo = a.fuse_hi = 0; /* products must stay below 2^52 */
         a.log2thr = ctx->d_log2thr;
         a.rec = (int32_t*)ctx->rec.p + k.unit0 * rec_words;
@@ -694,7 +694,7 @@ static int analyze_device_impl(flacmi_ctx* ctx, const flacmi_batch* b, const fla
         if (ebound) {
             double* w = nullptr;
             if (get_window(ctx, k.n, &w, nullptr, nullptr, &a.chunk_weight)) return hipErrorOutOfMemory;
-            a.bound = (const uint32_t*)ctx->bound.p + 2 * k.unit0;
+            a.bound = (const uint32_t*)ctx->bound.p + kBoundWords * k.unit0;
             a.energy = energy;
         }
         a.sign_bound = !(p->reserved[1] & FLACMI_FLAG_TIERS_ONLY) && sign_bound_allowed();

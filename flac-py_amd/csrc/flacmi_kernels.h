@@ -32,9 +32,14 @@ struct LpcArgs {
     double* acf;             /* optional [count][33] */
     int32_t fuse_lo, fuse_hi; /* window[i] == 1.0 exactly for i in [fuse_lo, fuse_hi) and
                                  |x| < 2^26 (0, 0: no fused blocks), see k_lpc */
-    uint32_t* bound;         /* optional [count][2]: the energy bound's words for k_resid_stream (lpc_finish);
-                                the window then holds kBoundLags more values behind its pad: kappa_1 .. */
+    uint32_t* bound;         /* optional [count][kBoundWords]: the energy bound's words for k_resid_stream
+                                (lpc_finish); the window then holds kBoundLags more values behind its pad: kappa_1 .. */
 };
+/* a unit's row of bound words (32 bytes): 0, 1 the energy bound's pair over every order (or the
+ * unusable pair below); 2, 3 the same pair over orders 2 .. L alone ((0, 0): L = 1, no such order,
+ * which passes); 4 order 1's coefficient and shift, (uint16)c_1 | shift_1 << 16; 5 .. 7 zero.
+ * Words 2 .. 4 mean nothing where words 0, 1 are unusable. */
+constexpr int kBoundWords = 8;
 /* the energy bound: the word pair of a unit it must not decide, and the lags
  * k = 1 .. kBoundLags of kappa_k = max_i |w_i - w_{i-k}| stored at window[n + kWindowPad ..] */
 constexpr uint32_t kBoundUnusable = 0xffffffffu;
@@ -89,10 +94,13 @@ struct ResidArgs {
     int32_t persist;                 /* k_resid kVarMf8: the grid loops over the batch and copies the next
                                         unit's samples into LDS (LDS-DMA) during this unit's Rice phase */
     int32_t sign_bound;              /* int8-MFMA pruning: try the sign-correlation bound before the tiers */
-    const uint32_t* bound;           /* k_resid_stream's batch kernel: k_lpc's energy-bound words [count][2] and */
+    const uint32_t* bound;           /* k_resid_stream's batch kernel: k_lpc's bound words [count][kBoundWords] and */
     const uint16_t* chunk_weight;    /* [n / 8] floor(256 min window weight) per 8-sample chunk (NULL: no pre-test) */
-    int32_t energy;                  /* knob FLACMI_ENERGY_BOUND: 1 = pre-test, then the tiers; 2 = pre-test, then
-                                        the exact pass; 0 = the tiers alone */
+    int32_t energy;                  /* knob FLACMI_ENERGY_BOUND: 1 = both pre-tests (the energy bound over every
+                                        order, then orders 2 .. L by it and order 1 by the closed form), then the
+                                        tiers; 2 = the first pre-test, then the exact pass; 3 = both, then the exact
+                                        pass; 4 = the first, then the tiers; 0 = the tiers alone.  Bit 0: the second
+                                        pre-test runs; bit 1: an undecided unit skips the tiers */
     int64_t list_off;                /* k_resid_stream's pre-test build lists unit gid as gid + list_off (set by
                                         the launchers: launch_stream_class_batch) */
 };

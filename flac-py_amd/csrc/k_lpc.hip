@@ -46,7 +46,10 @@ __device__ __forceinline__ void write_quant(int32_t* rec, int L, int p, const in
  * terms are exact below 2^24, so its test is true exactly when this sum exceeds kCoefLimit.
  * The pair's second word then is kBoundOutside: the stream kernel skips its fixed group for
  * such a unit (a listed unit's sums come from the list kernel) and goes straight to its own
- * test, which stays the one that lists. */
+ * test, which stays the one that lists.
+ * Beside the pair, for the stream kernel's second test ("order 1 apart"): the same two
+ * maxima over orders 2 .. L alone, rounded up the same way ((0, 0) for L = 1: no such order), and
+ * order 1's coefficient and shift in one word; see kBoundWords for the row. */
 template <int LMAX, bool EB = false>
 __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const LpcArgs& a, int32_t* __restrict__ rec,
                                            uint32_t* __restrict__ bound = nullptr) {
@@ -55,6 +58,7 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
     const __attribute__((address_space(4))) double* kap =
         (const __attribute__((address_space(4))) double*)a.window + a.n + kWindowPad - 1; /* kap[k], k = 1 .. 13 */
     double emax = 0.0, u2max = 0.0, samax = 0.0;
+    double emax2 = 0.0, u2max2 = 0.0; /* orders 2 .. L */
     bool ebad = false;
     const pym::PowTables PT{c_log_hdr, c_log_tab, c_exp_hdr, c_exp_tab};
     double c[LMAX + 1];
@@ -175,6 +179,10 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
                                     ebad |= !(en >= 0.0 && en < 0x1p80 && u2 < 0x1p40);
                                     emax = en > emax ? en : emax;
                                     u2max = u2 > u2max ? u2 : u2max;
+                                    if constexpr (k > 0) {
+                                        emax2 = en > emax2 ? en : emax2;
+                                        u2max2 = u2 > u2max2 ? u2 : u2max2;
+                                    }
                                 }
                             }
                         }
@@ -198,8 +206,16 @@ __device__ __forceinline__ void lpc_finish(const double (&acc)[LMAX + 1], const 
             const bool ok = st == ST_OK && negmask == 0 && !ebad && samax <= (double)kCoefLimit && u1 < 4294967295.0 &&
                             u2 < 4294967295.0;
             const bool out = st == ST_OK && samax > (double)kCoefLimit;
-            *reinterpret_cast<uint2*>(bound) =
-                ok ? uint2{(uint32_t)u1, (uint32_t)u2} : uint2{kBoundUnusable, out ? kBoundOutside : kBoundUnusable};
+            /* (each of the second pair's maxima is at most the first's: below 2^32 where ok) */
+            const double v1 = L > 1 ? __builtin_ceil(__builtin_sqrt((double)a.n * emax2) * (1.0 + 0x1p-40)) + 1.0 : 0.0;
+            const double v2 = L > 1 ? __builtin_ceil(256.0 * u2max2 * (1.0 + 0x1p-40)) + 1.0 : 0.0;
+            const uint32_t w0 = ok ? (uint32_t)u1 : kBoundUnusable, w1 = ok ? (uint32_t)u2 : out ? kBoundOutside : kBoundUnusable;
+            const uint32_t w2 = ok ? (uint32_t)v1 : 0u, w3 = ok ? (uint32_t)v2 : 0u;
+            /* order 1's coefficient and shift, as this lane wrote them into the record (held in a register
+             * across the orders instead, the word cost the int16 builds 12 bytes of scratch) */
+            const uint32_t w4 = ok ? ((uint32_t)rec[2 + L] & 0xffffu) | (uint32_t)rec[2] << 16 : 0u;
+            reinterpret_cast<uint4*>(bound)[0] = uint4{w0, w1, w2, w3};
+            reinterpret_cast<uint4*>(bound)[1] = uint4{w4, 0u, 0u, 0u};
         }
     }
 }
@@ -412,7 +428,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lpc_waves(L
     } /* !ACF_IN */
 
     constexpr bool EB = !ACF_IN && LMAX <= 12 && sizeof(SampleT) == 2;
-    lpc_finish<LMAX, EB>(acc, a, rec, EB && a.bound ? a.bound + 2 * gid : nullptr);
+    lpc_finish<LMAX, EB>(acc, a, rec, EB && a.bound ? a.bound + kBoundWords * gid : nullptr);
 }
 
 
@@ -555,7 +571,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LMAX <= 12 
 #pragma unroll
         for (int l = 0; l < 33; ++l) o[l] = (l <= LMAX && l <= L) ? acc[l < LMAX ? l : LMAX] : 0.0;
     }
-    lpc_finish<LMAX, (LMAX <= 12)>(acc, a, rec, a.bound ? a.bound + 2 * gid : nullptr);
+    lpc_finish<LMAX, (LMAX <= 12)>(acc, a, rec, a.bound ? a.bound + kBoundWords * gid : nullptr);
 }
 
 
@@ -584,7 +600,7 @@ static hipError_t launch_lpc_T(const LpcArgs& a, hipStream_t s) {
             r.unit0 += full;
             r.count = a.count - full;
             r.rec += full * a.rec_words;
-            if (r.bound) r.bound += 2 * full;
+            if (r.bound) r.bound += kBoundWords * full;
             if (r.acf) r.acf += full * 33;
             hipLaunchKernelGGL((k_lpc<LMAX, int16_t>), dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, s, r);
             return hipGetLastError();

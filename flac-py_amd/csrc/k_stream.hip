@@ -363,7 +363,10 @@ __device__ __forceinline__ void store_meta(flacmi_unit_meta* m, int lane, const 
  * LPC record but its status word is read before the pre-test: only an undecided unit builds the
  * tap table and the LPC operands and takes the exactness test (k_lpc marks every unit that test
  * lists unusable, so none is decided first), then runs tier 0 as a loop of its own and the
- * tiers as before (a.energy == 2: the exact pass at once). */
+ * tiers as before (a.energy bit 1: the exact pass at once).  Between the two (a.energy bit 0), where
+ * the pre-test fails on usable words: the same bound for orders 2 .. L alone and a closed form on
+ * the fixed sums F0 and F1 for order 1, from three more of k_lpc's words; a unit both decide takes
+ * the pre-test's decided path. */
 template <int NG, bool R05, int NFIX, bool LIST, bool EB, typename Args>
 __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, unsigned char* smem) {
     /* NFIX: the block length (and L = 4 NG, the workgroup size) as compile-time constants, the
@@ -403,14 +406,17 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
      * loop of its own.  (The fixed-only build shares no A operand either, but config 5 is bound by
      * HBM, not by VALU issue: measured with it, 0.02 ms per step slower in 4 of 5 rounds) */
     constexpr bool S8 = FLACMI_FIXED_STRIDE8 && EB;
-    /* EB: the record's status word and k_lpc's two words, workgroup-uniform and read before any
+    /* EB: the record's status word and k_lpc's five bound words, workgroup-uniform and read before any
      * store or barrier of the kernel: scalar loads that land during staging (used after B1) */
     constexpr bool EL = FLACMI_ENTRY_LOADS && EB;
     int st_entry = 0;
     uint2 bw_entry{0u, 0u};
+    uint32_t b2_entry[3] = {0u, 0u, 0u}; /* the row's words 2 .. 4 (kBoundWords): the second test's */
     if constexpr (EL) {
         st_entry = (a.rec + gid * rw)[0];
-        bw_entry = *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
+        bw_entry = *reinterpret_cast<const uint2*>(a.bound + kBoundWords * gid);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) b2_entry[i] = a.bound[kBoundWords * gid + 2 + i];
     }
 
     /* ---- stage: biased samples and the record into LDS, sum|x| on the way (EB: no record
@@ -443,6 +449,8 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
             st_entry = (int)opaque_s((uint32_t)st_entry);
             bw_entry.x = opaque_s(bw_entry.x);
             bw_entry.y = opaque_s(bw_entry.y);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) b2_entry[i] = opaque_s(b2_entry[i]);
         }
         uint32_t cwv[EB ? kSCPT : 1]; /* the chunks' weights (1/256) */
         if constexpr (EB) {
@@ -548,7 +556,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
      * MFMA bound, so it will be listed below and its fixed sums would be thrown away: the fixed
      * group is skipped */
     uint2 bw{0u, 0u};
-    if constexpr (EB) bw = EL ? bw_entry : *reinterpret_cast<const uint2*>(a.bound + 2 * gid);
+    if constexpr (EB) bw = EL ? bw_entry : *reinterpret_cast<const uint2*>(a.bound + kBoundWords * gid);
     const bool listed = EB && bw.x == kBoundUnusable && bw.y == kBoundOutside;
 
     /* ---- candidate sums on MFMA ----
@@ -872,7 +880,29 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                     const uint64_t f0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tj >> 32), 0) << 32) |
                                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tj, 0);
                     const uint64_t rhs = 256ull * ((uint64_t)bw.x + (uint64_t)n + fmin) + (uint64_t)bw.y * f0;
-                    if (bw.x != kBoundUnusable && 16ull * wr > rhs) {
+                    bool decided = bw.x != kBoundUnusable && 16ull * wr > rhs;
+                    /* The second test (a.energy bit 0), where the first fails on usable words: order 1 apart
+                     * (DESIGN §4).  Orders 2 .. L by the same bound on their own pair (both words zero: L = 1,
+                     * no such order); order 1 by a closed form on the exact fixed sums F0 and F1 (lane 1):
+                     * with its coefficient c and shift s, 2^s r_i = (2^s - c) x_i + c (x_i - x_{i-1}) + 2^s f,
+                     * f in [0, 1), so 2^s sum |r_i| >= |2^s - c| (F0 - 32768) - |c| F1 - 2^s n.  Both against
+                     * fmin + 3 n: the tiers' bound after four quarters is at least exact - 2 n - 1024, so a unit
+                     * decided here is one the tiers decide too.  Every term below 2^50. */
+                    if (!decided && bw.x != kBoundUnusable && (a.energy & 1)) {
+                        uint32_t b2[3];
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) b2[i] = EL ? b2_entry[i] : a.bound[kBoundWords * gid + 2 + i];
+                        const uint64_t f1 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(tj >> 32), 1) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tj, 1);
+                        const uint64_t thr = fmin + 3ull * (uint64_t)n;
+                        const uint64_t rhs2 = 256ull * ((uint64_t)b2[0] + (uint64_t)n + thr) + (uint64_t)b2[1] * f0;
+                        const int64_t c1 = (int64_t)(int16_t)(b2[2] & 0xffffu), p2s = (int64_t)1 << (b2[2] >> 16);
+                        const uint64_t ac = (uint64_t)(c1 < 0 ? -c1 : c1), ad = (uint64_t)(p2s - c1 < 0 ? c1 - p2s : p2s - c1);
+                        const uint64_t lhs1 = ad * (f0 > 32768ull ? f0 - 32768ull : 0ull);
+                        const uint64_t rhs1 = ac * f1 + (uint64_t)p2s * ((uint64_t)n + thr);
+                        decided = ((b2[0] | b2[1]) == 0u || 16ull * wr > rhs2) && lhs1 > rhs1;
+                    }
+                    if (decided) {
                         pruned = true;
                         tiers = false;
                         mv.tiers = 1 | (4 << 8);
@@ -943,7 +973,7 @@ __device__ __forceinline__ void stream_unit(const Args& a, const int64_t gid, un
                             }
                             return;
                         }
-                        if (a.energy == 2) {
+                        if (a.energy & 2) {
                             tiers = false; /* (tests, hit-rate counts) straight to the exact pass */
                         } else {
                             /* tier 0 after all: the LPC groups (bound) over the wave's blocks k % 4 == 0,

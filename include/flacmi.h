@@ -949,8 +949,11 @@ int flacmi_timing_reset(flacmi_ctx* ctx);
  * threads, 7 = as 2 with the one-window writer on its 16 KB window only), "FLACMI_DECODE_LPC"
  * (0 = no second fast-decoder pass for LPC subframes: those frames go to the general decoder
  * kernel; default 1), "FLACMI_ENERGY_BOUND" (the stream kernel's pruning calls: 1 = prove LPC's
- * loss from the autocorrelation first, then the partial-sum tiers (default); 0 = the tiers
- * alone; 2 = that proof, then the exact sums; same results but for meta.lpc_tiers),
+ * loss from the autocorrelation first, then, where that fails, for orders 2 .. L alone with
+ * order 1 by a closed form on the fixed sums, then the partial-sum tiers (default); 0 = the
+ * tiers alone; 2 = the first proof, then the exact sums; 3 = both proofs, then the exact sums;
+ * 4 = the first proof, then the tiers; same results but for meta.lpc_tiers, and under 2 and 3
+ * the exact LPC order and sum of a unit the tiers would have pruned),
  * "FLACMI_INFO_GRID" (cap on k_frame_info's grid in workgroups of 64 frames, 0 = the default
  * 2048; tests force a grid-stride loop with it).
  * FLACMI_E_INVALID for any other name.  No device needed. */
