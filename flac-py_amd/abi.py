@@ -278,6 +278,24 @@ class StreamResult(C.Structure):
     ]
 
 
+class RecompressResult(C.Structure):
+    _fields_ = [
+        ("frames", C.c_int64),
+        ("samples", C.c_int64),
+        ("consumed", C.c_int64),
+        ("status", C.c_int32),
+        ("site", C.c_int32),
+        ("candidates", C.c_int64),
+        ("probes", C.c_int64),
+        ("pass2_frames", C.c_int64),
+        ("blocks_out", C.c_int64),
+        ("frame_bytes", C.c_int64),
+        ("carry", C.c_int32),
+        ("sample_bits", C.c_int32),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
 class FrameInfo(C.Structure):
     _fields_ = [
         ("offset", C.c_int64),
@@ -398,6 +416,13 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p]),
     "flacmi_pcm_out_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "flacmi_units_out_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "flacmi_recompress_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DecodeParams),
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params),
+                                         C.POINTER(FrameParams), C.POINTER(RecompressResult)]),
+    "flacmi_recompress_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "flacmi_host_chain_walk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                          C.POINTER(Walk), C.c_void_p, C.c_int64]),
     "flacmi_decode_stream_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DecodeParams),

@@ -483,6 +483,70 @@ class Analyzer:
         torch.cuda.synchronize(dev)
         return out.cpu().numpy(), st.cpu().numpy()[:len(block_sizes)], total
 
+    def units_out(self, frames, channels: int, first_sample: int, block_len: int, n_blocks: int, tail_len: int,
+                  sample_size: int, sample_bytes: int, stride: int = 0, guard: int = 64, fill: int = 0x5A, firsts=None):
+        """flacmi_units_out_device alone.  frames: a list of (int32 array [channels][block_size], row
+        pitch) in stream order, each placed on the device at its own pitch (firsts: their first samples
+        when they do not simply follow one another); the unit rows lie
+        between two guard regions of `guard` elements and every byte of the buffer is `fill`
+        beforehand.  -> (the whole buffer as a 1-D array of the unit type, the index of unit 0's
+        first element in it, the pitch, status per frame, the width word)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        dt = np.int16 if sample_bytes == 2 else np.int32
+        stride = stride or unit_stride(block_len, sample_bytes)
+        n_units = (n_blocks + (1 if tail_len else 0)) * channels
+        keep = []
+        t = np.zeros(len(frames), dtype=abi.PCM_FRAME_DTYPE)
+        first = 0
+        for f, (x, pitch) in enumerate(frames):
+            x = np.asarray(x, dtype=np.int32).reshape(channels, -1)
+            bs = x.shape[1]
+            rows = np.full((channels, pitch), 0x7BADBAD, dtype=np.int32)  # what lies past a frame's length
+            rows[:, :bs] = x
+            r = torch.from_numpy(rows).to(dev)
+            keep.append(r)
+            if firsts is not None:
+                first = firsts[f]
+            t[f] = (r.data_ptr(), pitch, first, bs, 0)
+            first += bs
+        tab = torch.from_numpy(t.view(np.uint8).copy()).to(dev) if len(frames) else torch.zeros(8, dtype=torch.uint8, device=dev)
+        guard = ((guard * sample_bytes + 15) // 16) * 16 // sample_bytes
+        buf = torch.from_numpy(np.full((2 * guard + max(n_units, 1) * stride) * sample_bytes, fill, dtype=np.uint8)).to(dev)
+        st = torch.full((max(len(frames), 1),), -1, dtype=torch.int32, device=dev)
+        w = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self.lib.flacmi_units_out_device(self.ctx, tab.data_ptr() if len(frames) else None, len(frames), channels,
+                                               first_sample, block_len, n_blocks, tail_len, sample_size,
+                                               buf.data_ptr() + guard * sample_bytes, sample_bytes, stride,
+                                               st.data_ptr(), w.data_ptr(), stream), "flacmi_units_out_device")
+        torch.cuda.synchronize(dev)
+        return (buf.cpu().numpy().view(dt), guard, stride, st.cpu().numpy()[:len(frames)],
+                int(w.cpu().numpy().view(np.uint32)[0]))
+
+    def recompress_chunk(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
+                         check_crc: bool, max_block_size: int, final_chunk: bool, restart: bool, block_len: int,
+                         params: abi.Params, fp: abi.FrameParams, spec_wasted_bits: bool = False, out_alloc=None):
+        """flacmi_recompress_host + flacmi_recompress_fetch: one chunk of host stream bytes ->
+        (result, frame bytes, frame offsets [blocks_out + 1], frame status [blocks_out]).  out_alloc(nbytes)
+        -> a uint8 array of at least nbytes for the frame bytes (page-locked memory copies at PCIe rate)."""
+        dp = abi.DecodeParams()
+        dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, int(check_crc)
+        dp.reserved0 = abi.DECODE_WASTED_SPEC if spec_wasted_bits else 0
+        res = abi.RecompressResult()
+        check(self.lib.flacmi_recompress_host(self.ctx, data_ptr, nbytes, first_byte, C.byref(dp), max_block_size,
+                                              int(final_chunk), int(restart), block_len, C.byref(params), C.byref(fp),
+                                              C.byref(res)), "flacmi_recompress_host")
+        nb = int(res.blocks_out)
+        offsets = np.zeros(nb + 1, dtype=np.int64)
+        status = np.zeros(max(nb, 1), dtype=np.int32)
+        out = (out_alloc(int(res.frame_bytes))[:int(res.frame_bytes)] if out_alloc is not None
+               else np.empty(int(res.frame_bytes), dtype=np.uint8))
+        check(self.lib.flacmi_recompress_fetch(self.ctx, offsets.ctypes.data, status.ctypes.data, nb,
+                                               out.ctypes.data if out.size else None, out.size),
+              "flacmi_recompress_fetch")
+        return res, out, offsets, status[:nb]
+
     def decode_stream(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
                       check_crc: bool, max_block_size: int, final_chunk: bool, pcm_ptr: int, pcm_capacity: int,
                       raw: bool, bytes_per_sample: int, spec_wasted_bits: bool = False) -> abi.StreamResult:

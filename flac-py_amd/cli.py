@@ -17,6 +17,18 @@ packed on the device (decoder.decode_wav over flacmi_decode_stream_host) and wri
 the wave module as the reference does; --check-crc also verifies CRC-8 / CRC-16, which the
 reference reads unchecked.
 
+    python -m flac_amd recompress infile.flac outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
+                                                            [--fixed-only] [--fallback] [--stereo] [--lpc-sign]
+                                                            [--wasted-bits] [--rice-search] [--size-choice]
+                                                            [--check-crc] [--spec-wasted-bits] [--keep-metadata]
+                                                            [--device N]
+
+recompress (flac_amd.recompress over flacmi_recompress_host): the stream decoded and encoded again
+with encode's parameters and mode switches, its samples never leaving the device; --keep-metadata
+copies the input's metadata blocks (but a SEEKTABLE) and its MD5.  Where the input stops or a block
+cannot be written, what was produced before is written, the exception is printed and the exit
+status is 1.
+
     python -m flac_amd analyze infile.flac [--partitions] [--json] [--summary-only] [--device N]
 
 analyze (flac_amd.info over flacmi_info_stream_host): tab-separated key=value lines in stream
@@ -85,6 +97,28 @@ def make_argument_parser():
     dec.add_argument("--spec-wasted-bits", action="store_true",
                      help="read a subframe's wasted bits as the format codes them and shift them back in (the "
                           "reference reads one too few and leaves the samples unshifted)")
+    rec = action.add_parser("recompress", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    rec.add_argument("infile", type=Path, metavar="infile.flac")
+    rec.add_argument("outfile", type=Path, metavar="outfile.flac")
+    rec.add_argument("-b", "--block-size", type=int, default=DEFAULT_BLOCK_SIZE, metavar="N")
+    rec.add_argument("-l", "--max-lpc-order", type=int, default=DEFAULT_MAX_LPC_ORDER, metavar="N")
+    rec.add_argument("-q", "--qlp-coeff-precision", type=int, default=DEFAULT_QLP_COEFF_PRECISION, metavar="N")
+    rec.add_argument("-r", "--rice-partition-order", type=argparse_range, default=DEFAULT_RICE_PARTITION_ORDER,
+                     metavar="[M,]N")
+    for flag, text in (("--fixed-only", "fixed predictors only"),
+                       ("--fallback", "CONSTANT / VERBATIM subframes where the reference cannot write one"),
+                       ("--stereo", "stereo decorrelation (two-channel input)"),
+                       ("--lpc-sign", "corrected LPC predictor sign"),
+                       ("--wasted-bits", "wasted-bits subframes"),
+                       ("--rice-search", "exact Rice search"),
+                       ("--size-choice", "subframe choice by exact written size (needs --rice-search)")):
+        rec.add_argument(flag, action="store_true", help=text + " (as encode's switch)")
+    rec.add_argument("--check-crc", action="store_true", help="verify the input frames' CRC-8 and CRC-16")
+    rec.add_argument("--spec-wasted-bits", action="store_true",
+                     help="read the input's wasted bits as the format codes them and shift them back in")
+    rec.add_argument("--keep-metadata", action="store_true",
+                     help="copy the input's metadata blocks (all but a SEEKTABLE) and its MD5 signature")
+    rec.add_argument("--device", type=int, default=0)
     ana = action.add_parser("analyze", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     ana.add_argument("infile", type=Path, metavar="infile.flac")
     ana.add_argument("--partitions", action="store_true", help="list every subframe's Rice parameters")
@@ -145,6 +179,28 @@ def cmd_decode(args) -> None:
     print(f"Decoding completed in {seconds:.6g} seconds")
 
 
+def cmd_recompress(args) -> int:
+    from .encoder import EncoderParameters
+    from .recompress import recompress
+    parameters = EncoderParameters(block_size=args.block_size, lpc_order=range(args.max_lpc_order + 1),
+                                   qlp_precision=args.qlp_coeff_precision,
+                                   rice_partition_order=args.rice_partition_order)
+    t0 = timer()
+    with args.outfile.open("wb") as f:
+        try:
+            for bs in recompress(args.infile, parameters, device=args.device, check_crc=args.check_crc,
+                                 spec_wasted_bits=args.spec_wasted_bits, keep_metadata=args.keep_metadata,
+                                 fixed_only=args.fixed_only, fallback=args.fallback, stereo=args.stereo,
+                                 lpc_sign=args.lpc_sign, wasted=args.wasted_bits, rice_search=args.rice_search,
+                                 size_choice=args.size_choice):
+                f.write(bs)
+        except Exception as e:  # noqa: BLE001  -- what was produced before it is written, as analyze reports
+            print(f"stopped\texception={type(e).__name__}\tmessage={e}")
+            return 1
+    print(f"Recompression completed in {timer() - t0:.6g} seconds")
+    return 0
+
+
 def cmd_encode(args) -> None:
     from .encoder import EncoderParameters, encode_wav
     parameters = EncoderParameters(block_size=args.block_size, lpc_order=range(args.max_lpc_order + 1),
@@ -166,6 +222,8 @@ def main(argv=None) -> int:
         cmd_encode(args)
     if args.action == "decode":
         cmd_decode(args)
+    if args.action == "recompress":
+        return cmd_recompress(args)
     if args.action == "analyze":
         return cmd_analyze(args)
     return 0

@@ -171,6 +171,16 @@ struct flacmi_ctx {
     DevBuf h_side, h_choice;    /* flacmi_encode_host's side rows and per-frame choice (FLACMI_STEREO_BEST) */
     DevBuf idx, sd_data, sd_table, sd_meta, sd_rows, sd_pcm; /* frame index workspace; flacmi_decode_stream_host's buffers */
     DevBuf si_frames, si_subs, si_parts; /* flacmi_info_stream_host's candidate records */
+    /* flacmi_recompress_host: the frame list with its status words, the two carry buffers (int32 rows
+     * of channels x rc_stride; rc_cur holds rc_carry_len samples a channel), the blocks written since
+     * the last restart, and the last call's frame offsets / status for flacmi_recompress_fetch */
+    DevBuf rc_list, rc_carry[2];
+    int64_t rc_stride[2] = {0, 0};
+    int rc_cur = 0, rc_channels = 0;
+    int32_t rc_carry_len = 0;
+    int64_t rc_blocks = 0;
+    std::vector<int64_t> rc_offsets;
+    std::vector<int32_t> rc_status;
     int64_t frames_bytes = 0;   /* bytes of the last flacmi_encode_host call */
     static constexpr int kRing = 64;
     static constexpr int kMaxChunks = 8;
@@ -320,7 +330,8 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     for (auto& kv : ctx->chunk_weights) (void)hipFree(kv.second);
     for (DevBuf* b : {&ctx->bound, &ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->si_frames, &ctx->si_subs, &ctx->si_parts, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
                       &ctx->h_fs, &ctx->h_ls, &ctx->h_recs, &ctx->scan, &ctx->h_offsets, &ctx->h_status,
-                      &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice, &ctx->h_wasted})
+                      &ctx->h_frames, &ctx->h_subkind, &ctx->h_side, &ctx->h_choice, &ctx->h_wasted, &ctx->rc_list,
+                      &ctx->rc_carry[0], &ctx->rc_carry[1]})
         if (b->p) (void)hipFree(b->p);
     if (ctx->d_log2thr) (void)hipFree(ctx->d_log2thr);
     if (ctx->d_sintab) (void)hipFree(ctx->d_sintab);
@@ -1361,6 +1372,44 @@ int flacmi_pcm_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64
     return 0;
 }
 
+int flacmi_units_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64_t n_frames, int32_t channels,
+                            int64_t first_sample, int32_t block_len, int64_t n_blocks, int32_t tail_len,
+                            int32_t sample_size, void* units, int32_t sample_bytes, int64_t unit_stride,
+                            int32_t* frame_status, uint32_t* width, void* stream) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null argument");
+    if (n_frames < 0 || n_blocks < 0 || first_sample < 0) return fail(FLACMI_E_INVALID, "negative size");
+    if (channels < 1 || channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (block_len < 1 || block_len > FLACMI_MAX_BLOCK) return fail(FLACMI_E_INVALID, "block_len out of range");
+    if (tail_len < 0 || tail_len >= block_len) return fail(FLACMI_E_INVALID, "tail_len must be 0..block_len - 1");
+    if (sample_bytes != 2 && sample_bytes != 4) return fail(FLACMI_E_INVALID, "sample_bytes must be 2 or 4");
+    if (sample_size < 4 || sample_size > 8 * sample_bytes)
+        return fail(FLACMI_E_INVALID, "sample_size must be 4..%d for %d-byte rows", 8 * sample_bytes, sample_bytes);
+    if (unit_stride < block_len || (unit_stride * sample_bytes) % 16 != 0)
+        return fail(FLACMI_E_INVALID, "unit_stride must hold block_len samples and be a multiple of 16 bytes");
+    if (!width || (n_frames > 0 && (!frames || !frame_status))) return fail(FLACMI_E_INVALID, "null buffer");
+    if (((uintptr_t)frames & 7) != 0 || ((uintptr_t)units & 15) != 0 || (((uintptr_t)frame_status | (uintptr_t)width) & 3) != 0)
+        return fail(FLACMI_E_INVALID, "units must be 16-byte aligned, frames 8-byte, frame_status and width 4-byte");
+    const int64_t blocks = n_blocks + (tail_len > 0 ? 1 : 0);
+    if (blocks > 0x7FFFFFFF / channels) return fail(FLACMI_E_UNSUPPORTED, "more than 2^31 - 1 units in one call");
+    if (blocks > 0 && !units) return fail(FLACMI_E_INVALID, "null units");
+    if (int rc = set_device(ctx)) return rc;
+    UnitsArgs a{};
+    a.frames = frames;
+    a.n_frames = n_frames;
+    a.channels = channels;
+    a.block_len = block_len;
+    a.tail_len = tail_len;
+    a.sample_size = sample_size;
+    a.s0 = first_sample;
+    a.n_blocks = n_blocks;
+    a.units = units;
+    a.stride = unit_stride;
+    a.status = frame_status;
+    a.width = width;
+    HIP_TRY(launch_units(a, sample_bytes, (hipStream_t)stream));
+    return 0;
+}
+
 static inline bool walk_ref_error(int32_t st) { return st != 0 && (st & 0xFFFF) != FLACMI_STATUS_VERIFY; }
 
 int flacmi_host_chain_walk(const flacmi_frame_candidate* table, int64_t n_candidates, const int32_t* status,
@@ -1458,28 +1507,25 @@ struct ScopedDev { /* device scratch of one flacmi_decode_stream_host call */
 };
 }  // namespace
 
-int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
-                              const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
-                              uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
-                              flacmi_stream_result* res) {
-    if (!ctx || !dp || !res) return fail(FLACMI_E_INVALID, "null argument");
-    if (bytes < 0 || first_byte < 0 || first_byte > bytes || pcm_capacity < 0) return fail(FLACMI_E_INVALID, "bad size");
-    if (bytes > 0 && !data) return fail(FLACMI_E_INVALID, "null buffer");
-    if (pcm_capacity > 0 && !pcm) return fail(FLACMI_E_INVALID, "null pcm buffer");
-    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
-    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
-    if (int rc = decode_flags_ok(dp)) return rc;
-    if (max_block_size < 0 || max_block_size > FLACMI_MAX_BLOCK + 1) return fail(FLACMI_E_INVALID, "max_block_size must be 0..65536");
-    if (mode != FLACMI_PCM_PACKED && mode != FLACMI_PCM_RAW32) return fail(FLACMI_E_INVALID, "mode must be a flacmi_pcm_mode");
-    if (mode == FLACMI_PCM_PACKED && (bytes_per_sample < 1 || bytes_per_sample > 4))
-        return fail(FLACMI_E_INVALID, "bytes_per_sample must be 1..4");
-    memset(res, 0, sizeof(*res));
-    res->consumed = first_byte;
-    if (bytes == first_byte) return 0;
-    if (int rc = set_device(ctx)) return rc;
+/* Steps 1 to 5 of flacmi_decode_stream_host (copy in, index, pass 1, the chain walk with its
+ * probes, pass 2), shared with flacmi_recompress_host: the chain's first nc frames are decoded,
+ * frame i's rows are pass 2's (row2[i] >= 0: rows2 at stride2) or pass 1's (its candidate's, in
+ * ctx->sd_rows at stride1); stop is the status word of the frame at pos, or 0. */
+namespace {
+struct StreamFrames {
+    std::vector<flacmi_chain_frame> chain;
+    std::vector<int32_t> bsz;
+    std::vector<int64_t> row2;
+    ScopedDev rows2;
+    int64_t nc = 0, n2 = 0, stride1 = 4, stride2 = 4, pos = 0, candidates = 0, probes = 0;
+    int32_t stop = 0;
+};
+}  // namespace
+
+static int stream_frames(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                         const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk, StreamFrames& h) {
     hipStream_t s = ctx->stream;
     const int ch = dp->channels;
-    const int B = mode == FLACMI_PCM_RAW32 ? 4 : bytes_per_sample;
     flacmi_decode_params p1 = *dp;
     p1.first_frame = -1;
 
@@ -1499,7 +1545,7 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
         if (n <= cap) break;
         cap = n;
     }
-    res->candidates = n;
+    h.candidates = n;
     std::vector<flacmi_frame_candidate> table((size_t)n);
     if (n) HIP_TRY(hipMemcpy(table.data(), (char*)ctx->sd_table.p + 16, sizeof(flacmi_frame_candidate) * (size_t)n, hipMemcpyDeviceToHost));
 
@@ -1534,7 +1580,8 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
     }
 
     /* 4. the walk; a probe decodes the one frame at w.pos into rows of the largest block */
-    std::vector<flacmi_chain_frame> chain((size_t)n + 16);
+    std::vector<flacmi_chain_frame>& chain = h.chain;
+    chain.assign((size_t)n + 16, flacmi_chain_frame{});
     flacmi_walk w{};
     w.pos = first_byte;
     ScopedDev probe_rows, probe_meta;
@@ -1569,15 +1616,17 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
         w.probe_status = k1;
         /* the proposed end was the chunk's: ending anywhere before it is no finding yet */
         if (!walk_ref_error(k1) && (k1 >> 16) == FLACMI_DSITE_FRAME_END) w.probe_status = 0;
-        ++res->probes;
+        ++h.probes;
     }
     int64_t nc = w.n_chain;
     int32_t stop = w.state == FLACMI_WALK_STOPPED ? w.stop_status : 0;
 
     /* block sizes; 5. pass 2: the chain frames whose pass-1 rows are not final, in runs of
      * neighbours, with the chain's own offsets */
-    std::vector<int32_t> bsz((size_t)nc);
-    std::vector<int64_t> row2((size_t)nc, -1); /* index among the pass-2 frames */
+    std::vector<int32_t>& bsz = h.bsz;
+    std::vector<int64_t>& row2 = h.row2; /* index among the pass-2 frames */
+    bsz.assign((size_t)nc, 0);
+    row2.assign((size_t)nc, -1);
     int64_t n2 = 0, stride2 = 4;
     for (int64_t i = 0; i < nc; ++i) {
         const flacmi_chain_frame& c = chain[i];
@@ -1593,8 +1642,9 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
             stride2 = std::max<int64_t>(stride2, (bsz[i] + 3) & ~3);
         }
     }
-    res->pass2_frames = n2;
-    ScopedDev rows2, meta2;
+    h.n2 = n2;
+    ScopedDev& rows2 = h.rows2;
+    ScopedDev meta2;
     if (n2) {
         if (int rc = rows2.alloc(sizeof(int32_t) * (size_t)n2 * ch * (size_t)stride2)) return rc;
         if (int rc = meta2.alloc(32 * (size_t)n2 + 64)) return rc;
@@ -1634,6 +1684,53 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
             }
         }
     }
+
+    h.nc = nc;
+    h.stop = stop;
+    h.stride1 = stride1;
+    h.stride2 = stride2;
+    h.pos = w.pos;
+    return 0;
+}
+
+int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                              const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
+                              uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
+                              flacmi_stream_result* res) {
+    if (!ctx || !dp || !res) return fail(FLACMI_E_INVALID, "null argument");
+    if (bytes < 0 || first_byte < 0 || first_byte > bytes || pcm_capacity < 0) return fail(FLACMI_E_INVALID, "bad size");
+    if (bytes > 0 && !data) return fail(FLACMI_E_INVALID, "null buffer");
+    if (pcm_capacity > 0 && !pcm) return fail(FLACMI_E_INVALID, "null pcm buffer");
+    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
+    if (max_block_size < 0 || max_block_size > FLACMI_MAX_BLOCK + 1) return fail(FLACMI_E_INVALID, "max_block_size must be 0..65536");
+    if (mode != FLACMI_PCM_PACKED && mode != FLACMI_PCM_RAW32) return fail(FLACMI_E_INVALID, "mode must be a flacmi_pcm_mode");
+    if (mode == FLACMI_PCM_PACKED && (bytes_per_sample < 1 || bytes_per_sample > 4))
+        return fail(FLACMI_E_INVALID, "bytes_per_sample must be 1..4");
+    memset(res, 0, sizeof(*res));
+    res->consumed = first_byte;
+    if (bytes == first_byte) return 0;
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int ch = dp->channels;
+    const int B = mode == FLACMI_PCM_RAW32 ? 4 : bytes_per_sample;
+    StreamFrames h;
+    {
+        const int rc = stream_frames(ctx, data, bytes, first_byte, dp, max_block_size, final_chunk, h);
+        res->candidates = h.candidates;
+        res->probes = h.probes;
+        res->pass2_frames = h.n2;
+        if (rc) return rc;
+    }
+    const std::vector<flacmi_chain_frame>& chain = h.chain;
+    const std::vector<int32_t>& bsz = h.bsz;
+    const std::vector<int64_t>& row2 = h.row2;
+    const ScopedDev& rows2 = h.rows2;
+    const int64_t stride1 = h.stride1, stride2 = h.stride2;
+    int64_t nc = h.nc;
+    int32_t stop = h.stop;
+    struct { int64_t pos; } w{h.pos};
 
     /* 6. PCM: the frames that fit the caller's buffer */
     std::vector<flacmi_pcm_frame> pf((size_t)nc);
@@ -1878,37 +1975,30 @@ int flacmi_info_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes,
     return 0;
 }
 
-int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_params* params,
-                       const flacmi_frame_params* fp, int64_t* frame_offsets, int32_t* frame_status) {
-    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
-    int64_t nf = 0;
-    if (int rc = validate_frames(batch, fp, &nf)) return rc;
-    if (!params || !frame_offsets || !frame_status) return fail(FLACMI_E_INVALID, "null argument");
-    flacmi_params sized;
-    if (int rc = size_choice_params(params, fp, &sized)) return rc;
-    params = &sized;
-    ctx->frames_bytes = 0;
-    if (nf == 0) {
-        frame_offsets[0] = 0;
-        return 0;
-    }
-    if (int rc = set_device(ctx)) return rc;
-    const size_t nu = (size_t)batch->n_units;
-    const bool stereo = stereo_on(fp);
+/* The context buffers encode_rows writes (everything but the sample rows, which its caller fills) */
+static int encode_rows_buffers(flacmi_ctx* ctx, size_t nu, int64_t nf, const flacmi_params* params,
+                               const flacmi_frame_params* fp) {
     const size_t nou = stereo_out_units(fp, nu); /* units of the analysis outputs */
-    const int64_t sstride = row_pitch(batch->block_len, batch->sample_bytes);
     const int64_t pstride = (1LL << (params->rice_max > 0 ? params->rice_max : 0)) + 1;
-    if (int rc = ensure_buf(ctx->h_samples, stereo_sample_rows(fp, nu) * sstride * batch->sample_bytes)) return rc;
     if (int rc = ensure_buf(ctx->h_meta, nou * sizeof(flacmi_unit_meta))) return rc;
     if (int rc = ensure_buf(ctx->h_params, nou * pstride * sizeof(int32_t))) return rc;
     if (int rc = ensure_buf(ctx->h_offsets, sizeof(int64_t) * (size_t)(nf + 1))) return rc;
     if (int rc = ensure_buf(ctx->h_status, sizeof(int32_t) * (size_t)nf)) return rc;
-    flacmi_batch db = *batch;
-    db.samples = ctx->h_samples.p;
-    db.unit_stride = sstride;
-    HIP_TRY(hipMemcpy2DAsync(ctx->h_samples.p, sstride * batch->sample_bytes, batch->samples,
-                             batch->unit_stride * batch->sample_bytes, batch->block_len * batch->sample_bytes, nu,
-                             hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+/* flacmi_encode_host behind its copy in, shared with flacmi_recompress_host: db is a device batch
+ * in ctx->h_samples (in the stereo mode with room for the mid rows behind it) that this call may
+ * shift in place (the wasted-bits mode, once per copy of the rows); params already went through
+ * size_choice_params.  The frames stay in ctx->h_frames, frame_offsets / frame_status are host
+ * arrays. */
+static int encode_rows(flacmi_ctx* ctx, const flacmi_batch& db, const flacmi_params* params,
+                       const flacmi_frame_params* fp, int64_t nf, int64_t* frame_offsets, int32_t* frame_status) {
+    const flacmi_batch* batch = &db;
+    const size_t nu = (size_t)db.n_units;
+    const bool stereo = stereo_on(fp);
+    const size_t nou = stereo_out_units(fp, nu);
+    const int64_t pstride = (1LL << (params->rice_max > 0 ? params->rice_max : 0)) + 1;
     if (int rc = wasted_shift(fp, db, ctx->h_wasted, ctx->stream)) return rc; /* once, before the redo loop */
     for (int rbytes = 4;; rbytes = 8) {
         const int64_t rstride = ((batch->block_len * rbytes + 15) / 16) * 16 / rbytes;
@@ -1956,6 +2046,229 @@ int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_
         ctx->frames_bytes = total;
         return 0;
     }
+}
+
+int flacmi_encode_host(flacmi_ctx* ctx, const flacmi_batch* batch, const flacmi_params* params,
+                       const flacmi_frame_params* fp, int64_t* frame_offsets, int32_t* frame_status) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
+    int64_t nf = 0;
+    if (int rc = validate_frames(batch, fp, &nf)) return rc;
+    if (!params || !frame_offsets || !frame_status) return fail(FLACMI_E_INVALID, "null argument");
+    flacmi_params sized;
+    if (int rc = size_choice_params(params, fp, &sized)) return rc;
+    params = &sized;
+    ctx->frames_bytes = 0;
+    if (nf == 0) {
+        frame_offsets[0] = 0;
+        return 0;
+    }
+    if (int rc = set_device(ctx)) return rc;
+    const size_t nu = (size_t)batch->n_units;
+    const int64_t sstride = row_pitch(batch->block_len, batch->sample_bytes);
+    if (int rc = ensure_buf(ctx->h_samples, stereo_sample_rows(fp, nu) * sstride * batch->sample_bytes)) return rc;
+    if (int rc = encode_rows_buffers(ctx, nu, nf, params, fp)) return rc;
+    flacmi_batch db = *batch;
+    db.samples = ctx->h_samples.p;
+    db.unit_stride = sstride;
+    HIP_TRY(hipMemcpy2DAsync(ctx->h_samples.p, sstride * batch->sample_bytes, batch->samples,
+                             batch->unit_stride * batch->sample_bytes, batch->block_len * batch->sample_bytes, nu,
+                             hipMemcpyHostToDevice, ctx->stream));
+    return encode_rows(ctx, db, params, fp, nf, frame_offsets, frame_status);
+}
+
+/* ---- recompress: stream_frames, k_units, encode_rows -------------------------------------
+ * The frame list of a call is the carry (a pseudo-frame at sample 0 over the current carry
+ * buffer) followed by the chain's frames.  The first k_units launch cuts it into the call's unit
+ * rows (ctx->h_samples, where flacmi_encode_host keeps its copy of the rows), the second writes
+ * the samples behind the last whole block into the other carry buffer, so each sample is
+ * range-checked by the call that decoded it.  A range finding in frame j stops the input there:
+ * the blocks entirely before j's first sample hold none of its samples and are already written. */
+int flacmi_recompress_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                           const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
+                           int32_t restart, int32_t block_len, const flacmi_params* params,
+                           const flacmi_frame_params* fp, flacmi_recompress_result* res) {
+    if (!ctx || !dp || !res || !params || !fp) return fail(FLACMI_E_INVALID, "null argument");
+    if (bytes < 0 || first_byte < 0 || first_byte > bytes) return fail(FLACMI_E_INVALID, "bad size");
+    if (bytes > 0 && !data) return fail(FLACMI_E_INVALID, "null buffer");
+    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
+    if (max_block_size < 0 || max_block_size > FLACMI_MAX_BLOCK + 1) return fail(FLACMI_E_INVALID, "max_block_size must be 0..65536");
+    if (block_len < 1 || block_len > FLACMI_MAX_BLOCK) return fail(FLACMI_E_INVALID, "block_len must be 1..65535");
+    /* whatever flacmi_encode_host refuses for these params / fp, on a batch of this shape */
+    const int sbytes = fp->sample_size <= 16 ? 2 : 4;
+    const int64_t sstride = row_pitch(block_len, sbytes);
+    flacmi_batch vb{};
+    vb.samples = (const void*)(uintptr_t)16;
+    vb.sample_bytes = sbytes;
+    vb.sample_bits = 2;
+    vb.unit_stride = sstride;
+    vb.block_len = block_len;
+    int64_t nf = 0;
+    if (int rc = validate_frames(&vb, fp, &nf)) return rc;
+    flacmi_params sized;
+    if (int rc = size_choice_params(params, fp, &sized)) return rc;
+    if (dp->channels != fp->channels || dp->sample_size != fp->sample_size)
+        return fail(FLACMI_E_INVALID, "dp and fp disagree on channels or sample_size");
+    {
+        flacmi_outputs vo{};
+        vo.meta = (flacmi_unit_meta*)(uintptr_t)16;
+        vo.rice_params = (int32_t*)(uintptr_t)16;
+        vo.residual = (void*)(uintptr_t)16;
+        vo.residual_bytes = 4;
+        vo.residual_stride = ((block_len * 4 + 15) / 16) * 16 / 4;
+        vo.params_stride = (1LL << (sized.rice_max > 0 ? sized.rice_max : 0)) + 1;
+        if (int rc = validate(&vb, &sized, &vo)) return rc;
+    }
+    const int ch = fp->channels, B = block_len;
+    memset(res, 0, sizeof(*res));
+    res->consumed = first_byte;
+    ctx->frames_bytes = 0;
+    ctx->rc_offsets.assign(1, 0);
+    ctx->rc_status.clear();
+    if (restart) {
+        ctx->rc_carry_len = 0;
+        ctx->rc_blocks = 0;
+    }
+    if (ctx->rc_carry_len > 0 && ctx->rc_channels != ch)
+        return fail(FLACMI_E_INVALID, "the carry holds %d channels, the call has %d: restart first", ctx->rc_channels, ch);
+    res->carry = ctx->rc_carry_len;
+    if (bytes == first_byte && !(final_chunk && ctx->rc_carry_len > 0)) return 0;
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+
+    StreamFrames h;
+    h.pos = first_byte;
+    if (bytes > first_byte) {
+        const int rc = stream_frames(ctx, data, bytes, first_byte, dp, max_block_size, final_chunk, h);
+        res->candidates = h.candidates;
+        res->probes = h.probes;
+        res->pass2_frames = h.n2;
+        if (rc) return rc;
+    }
+    int64_t nc = h.nc, pos = h.pos;
+    int32_t stop = h.stop;
+    const bool at_end = final_chunk && stop == 0;
+    const int32_t carry_in = ctx->rc_carry_len;
+    if (nc == 0 && stop == 0 && !at_end) return 0; /* no whole frame in the chunk: the carry stays */
+
+    /* the frame list */
+    const int64_t nl = nc + 1;
+    std::vector<flacmi_pcm_frame> pf((size_t)nl);
+    pf[0] = flacmi_pcm_frame{ctx->rc_carry[ctx->rc_cur].p, ctx->rc_stride[ctx->rc_cur], 0, carry_in, 0};
+    int64_t total = carry_in;
+    for (int64_t i = 0; i < nc; ++i) {
+        flacmi_pcm_frame& f = pf[(size_t)i + 1];
+        if (h.row2[i] >= 0) {
+            f.rows = (int32_t*)h.rows2.p + h.row2[i] * ch * h.stride2;
+            f.stride = h.stride2;
+        } else {
+            f.rows = (int32_t*)ctx->sd_rows.p + h.chain[i].candidate * ch * h.stride1;
+            f.stride = h.stride1;
+        }
+        f.first_sample = total;
+        f.block_size = h.bsz[i];
+        f.reserved0 = 0;
+        total += h.bsz[i];
+    }
+    int64_t n_blocks = total / B;
+    int32_t tail = at_end ? (int32_t)(total % B) : 0;
+    /* the samples behind the last whole block: range-checked even where a later frame's status drops them */
+    const int32_t rest = at_end ? 0 : (int32_t)(total % B);
+    int32_t left = stop == 0 ? rest : 0;
+
+    /* device words behind the list: status of the first launch [nl], of the second [nl], the two widths */
+    if (int rc = ensure_buf(ctx->rc_list, (sizeof(flacmi_pcm_frame) + 8) * (size_t)nl + 16)) return rc;
+    flacmi_pcm_frame* d_pf = (flacmi_pcm_frame*)ctx->rc_list.p;
+    int32_t* d_st1 = (int32_t*)(d_pf + nl);
+    int32_t* d_st2 = d_st1 + nl;
+    uint32_t* d_w = (uint32_t*)(d_st2 + nl);
+    HIP_TRY(hipMemcpyAsync(d_pf, pf.data(), sizeof(flacmi_pcm_frame) * (size_t)nl, hipMemcpyHostToDevice, s));
+    const size_t nu0 = (size_t)(n_blocks + (tail > 0 ? 1 : 0)) * ch;
+    if (nu0 > 0)
+        if (int rc = ensure_buf(ctx->h_samples, stereo_sample_rows(fp, nu0) * sstride * sbytes)) return rc;
+    if (int rc = flacmi_units_out_device(ctx, d_pf, nl, ch, 0, B, n_blocks, tail, fp->sample_size, ctx->h_samples.p, sbytes,
+                                         sstride, d_st1, d_w, s))
+        return rc;
+    std::vector<int32_t> st((size_t)(2 * nl), 0);
+    const int other = ctx->rc_cur ^ 1;
+    if (rest > 0) {
+        const int64_t cstride = row_pitch(B, 4);
+        if (int rc = ensure_buf(ctx->rc_carry[other], sizeof(int32_t) * (size_t)ch * cstride)) return rc;
+        ctx->rc_stride[other] = cstride;
+        if (int rc = flacmi_units_out_device(ctx, d_pf, nl, ch, n_blocks * B, B, 0, rest, fp->sample_size,
+                                             ctx->rc_carry[other].p, 4, cstride, d_st2, d_w + 1, s))
+            return rc;
+    }
+    uint32_t width = 0;
+    HIP_TRY(hipMemcpyAsync(st.data(), d_st1, sizeof(int32_t) * (size_t)(rest > 0 ? 2 * nl : nl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&width, d_w, sizeof(width), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t j = 0; j < nl; ++j) {
+        if ((st[j] | st[nl + j]) == 0) continue;
+        stop = (FLACMI_DSITE_PCM_RANGE << 16) | FLACMI_STATUS_OVERFLOW;
+        nc = j > 0 ? j - 1 : 0;
+        pos = j > 0 ? h.chain[j - 1].offset : first_byte;
+        total = pf[j].first_sample;
+        n_blocks = total / B;
+        tail = 0;
+        left = 0;
+        break;
+    }
+
+    /* the encode half over the blocks that stand */
+    nf = n_blocks + (tail > 0 ? 1 : 0);
+    if (nf > 0) {
+        int bl = 0;
+        while (bl < 32 && (width >> bl) != 0) ++bl;
+        flacmi_batch db{};
+        db.samples = ctx->h_samples.p;
+        db.sample_bytes = sbytes;
+        db.sample_bits = std::min<int>(fp->sample_size, std::max(2, bl + 1));
+        db.unit_stride = sstride;
+        db.n_units = nf * ch;
+        db.block_len = B;
+        db.tail_len = tail;
+        db.n_tail_units = tail > 0 ? ch : 0;
+        flacmi_frame_params f2 = *fp;
+        f2.first_frame = fp->first_frame + ctx->rc_blocks;
+        ctx->rc_offsets.assign((size_t)nf + 1, 0);
+        ctx->rc_status.assign((size_t)nf, 0);
+        if (int rc = encode_rows_buffers(ctx, (size_t)db.n_units, nf, &sized, &f2)) return rc;
+        if (int rc = encode_rows(ctx, db, &sized, &f2, nf, ctx->rc_offsets.data(), ctx->rc_status.data())) return rc;
+        ctx->rc_blocks += nf;
+        res->sample_bits = db.sample_bits;
+    }
+    if (left > 0) {
+        ctx->rc_cur = other;
+        ctx->rc_channels = ch;
+    }
+    ctx->rc_carry_len = left;
+    res->frames = nc;
+    res->samples = nc > 0 ? pf[(size_t)nc].first_sample + pf[(size_t)nc].block_size - carry_in : 0;
+    res->consumed = pos;
+    res->status = stop & 0xFFFF;
+    res->site = (stop >> 16) & 0xFFFF;
+    res->blocks_out = nf;
+    res->frame_bytes = ctx->frames_bytes;
+    res->carry = left;
+    return 0;
+}
+
+int flacmi_recompress_fetch(flacmi_ctx* ctx, int64_t* frame_offsets, int32_t* frame_status, int64_t n_blocks,
+                            uint8_t* out, int64_t bytes) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
+    if (n_blocks != (int64_t)ctx->rc_status.size())
+        return fail(FLACMI_E_INVALID, "the last flacmi_recompress_host call wrote %zu blocks", ctx->rc_status.size());
+    if (!frame_offsets || (n_blocks > 0 && !frame_status)) return fail(FLACMI_E_INVALID, "null argument");
+    if (bytes < 0 || bytes > ctx->frames_bytes || (bytes > 0 && !out))
+        return fail(FLACMI_E_INVALID, "the last flacmi_recompress_host call holds %lld bytes", (long long)ctx->frames_bytes);
+    memcpy(frame_offsets, ctx->rc_offsets.data(), sizeof(int64_t) * ((size_t)n_blocks + 1));
+    if (n_blocks > 0) memcpy(frame_status, ctx->rc_status.data(), sizeof(int32_t) * (size_t)n_blocks);
+    if (bytes == 0) return 0;
+    if (int rc = set_device(ctx)) return rc;
+    HIP_TRY(hipMemcpy(out, ctx->h_frames.p, (size_t)bytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 /* ---- pipelined host encode ---------------------------------------------------------

@@ -267,8 +267,22 @@ struct PcmArgs {
     int32_t* status;         /* [n_frames] */
 };
 
+/* Unit rows from decoded frames (k_units.hip): sample s >= s0 of channel c of the frame list
+ * goes to unit ((s - s0) / block_len) * channels + c, element (s - s0) % block_len; n_blocks
+ * whole blocks, then one block of tail_len samples when tail_len > 0 */
+struct UnitsArgs {
+    const flacmi_pcm_frame* frames; /* ordered by first_sample, no gaps */
+    int64_t n_frames;
+    int32_t channels, block_len, tail_len, sample_size;
+    int64_t s0, n_blocks;
+    void* units;             /* int16 or int32 rows, 16-byte aligned */
+    int64_t stride;          /* elements; a multiple of 16 bytes, >= block_len */
+    int32_t* status;         /* [n_frames] */
+    uint32_t* width;         /* one word: max over the samples written of x >= 0 ? x : ~x */
+};
+
 struct ResidLaunch {
-    int threads;             /* workgroup size (multiple of 64) */
+    int threads;            /* workgroup size (multiple of 64) */
     size_t lds_bytes;        /* dynamic LDS */
 };
 
@@ -387,6 +401,8 @@ hipError_t launch_index(const IndexArgs& a, hipStream_t s);
 hipError_t launch_frame_info(const InfoArgs& a, int grid_cap, hipStream_t s);
 int64_t index_scan_groups(int64_t n_tiles);
 hipError_t launch_pcm(const PcmArgs& a, hipStream_t s);
+/* clears a.status [n_frames] and a.width, then one workgroup per unit; sample_bytes 2 or 4 */
+hipError_t launch_units(const UnitsArgs& a, int32_t sample_bytes, hipStream_t s);
 
 hipError_t launch_selftest(int32_t which, const double* x, double* out, int32_t* status, int64_t n,
                            const double* log2thr, hipStream_t s);

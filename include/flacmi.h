@@ -697,6 +697,28 @@ int flacmi_pcm_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64
                           int32_t channels, int32_t bytes_per_sample, int32_t mode, uint8_t* out,
                           int64_t out_capacity, int32_t* frame_status, void* stream);
 
+/* The same frame list as the encoder's unit rows (k_units; the counterpart of the call above,
+ * for a stream that is decoded and encoded again without its samples leaving the device).  The
+ * frames follow one another without gaps, ordered by first_sample.  The unit timeline starts at
+ * sample first_sample (frames wholly before it are skipped): sample s >= first_sample of channel
+ * c goes to unit ((s - first_sample) / block_len) * channels + c, element
+ * (s - first_sample) % block_len.  n_blocks whole blocks are written, then, when tail_len > 0, one
+ * block of tail_len < block_len samples: n_units = (n_blocks + (tail_len > 0)) * channels rows of
+ * int16 (sample_bytes 2) or int32 (4) at a pitch of unit_stride elements (flacmi_unit_stride, or
+ * any multiple of 16 bytes that holds block_len; rows 16-byte aligned).  Every element of a
+ * written unit from its length to the pitch is written as 0, a sample no frame holds as 0;
+ * samples past the last unit are not read and nothing outside the n_units rows is written,
+ * whatever the frame list holds.  frame_status[f] (n_frames words) = FLACMI_STATUS_OVERFLOW
+ * where a sample of frame f that the call reads does not fit sample_size (4..32, at most
+ * 8 * sample_bytes) bits two's complement (the frame's samples are then unspecified in the
+ * units), else 0.  *width receives the maximum over the samples written of x >= 0 ? x : ~x: with
+ * k its bit length, min(sample_size, max(2, k + 1)) is the flacmi_batch.sample_bits of the rows.
+ * Device pointers, enqueued on `stream`. */
+int flacmi_units_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64_t n_frames,
+                            int32_t channels, int64_t first_sample, int32_t block_len, int64_t n_blocks,
+                            int32_t tail_len, int32_t sample_size, void* units, int32_t sample_bytes,
+                            int64_t unit_stride, int32_t* frame_status, uint32_t* width, void* stream);
+
 /* The walk from frame to frame over the candidate table and the first pass's results (plain
  * host code, no device: get_frames' loop, decoder.py:100-108, with each frame's end looked
  * up instead of reached by reading).  status[k] / frame_end[k] are candidate k's results from
@@ -772,6 +794,50 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
                               const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
                               uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
                               flacmi_stream_result* res);
+
+/* ---- recompress: .flac bytes in, .flac frames out, the samples stay on the device ------- */
+/* One chunk of a stream through the decoder above (steps copy in .. pass 2, same arguments:
+ * first_byte, dp with check_crc and FLACMI_DECODE_WASTED_SPEC, max_block_size, final_chunk) and,
+ * instead of the PCM kernel, through k_units into unit rows of block_len samples and
+ * flacmi_encode_host's analysis and frame writer (params and fp as there: every flag and mode,
+ * every refusal).  Only compressed bytes cross PCIe.
+ *
+ * The context keeps a carry: the fewer than block_len samples per channel behind the last whole
+ * block, as int32 rows, which open the next call's first block.  restart != 0 discards the carry
+ * and the block counter first (a new stream).  Block k of the stream (counted since the last
+ * restart) is written with the coded number fp->first_frame + k.  The unit rows are int16 when
+ * fp->sample_size <= 16, else int32; the frame bytes do not depend on that.
+ *
+ * A stopping frame is a decoder status (as flacmi_decode_stream_host reports it) or a sample
+ * that does not fit fp->sample_size bits (FLACMI_STATUS_OVERFLOW at FLACMI_DSITE_PCM_RANGE): the
+ * whole blocks that lie entirely before its first sample are encoded and delivered,
+ * res->consumed is its offset, and the carry is dropped.  With final_chunk set and the stream
+ * at its end the carry goes out as the short last block; a final call with bytes == first_byte
+ * does the same.  FLACMI_E_INVALID, before any device work, for whatever flacmi_encode_host
+ * refuses for the same params / fp, for block_len outside 1..FLACMI_MAX_BLOCK and for dp
+ * disagreeing with fp on channels or sample_size.
+ *
+ * The new frames stay in a context buffer, as flacmi_encode_host leaves them:
+ * flacmi_recompress_fetch copies frame_offsets [blocks_out + 1], frame_status [blocks_out] (as
+ * flacmi_frame_sizes_device: a failing block has no bytes) and the frame_bytes bytes out. */
+typedef struct flacmi_recompress_result {
+    int64_t frames;          /* input frames consumed */
+    int64_t samples;         /* samples per channel they hold */
+    int64_t consumed;        /* offset after the last of them */
+    int32_t status, site;    /* why the input stopped: 0, 0 = it has not */
+    int64_t candidates, probes, pass2_frames; /* as flacmi_stream_result */
+    int64_t blocks_out;      /* frames written by this call (failing ones included) */
+    int64_t frame_bytes;     /* their bytes */
+    int32_t carry;           /* samples per channel kept for the next call */
+    int32_t sample_bits;     /* the measured flacmi_batch.sample_bits of the call's unit rows (0: none) */
+    int64_t reserved[2];
+} flacmi_recompress_result;
+int flacmi_recompress_host(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
+                           const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
+                           int32_t restart, int32_t block_len, const flacmi_params* params,
+                           const flacmi_frame_params* fp, flacmi_recompress_result* res);
+int flacmi_recompress_fetch(flacmi_ctx* ctx, int64_t* frame_offsets, int32_t* frame_status, int64_t n_blocks,
+                            uint8_t* out, int64_t bytes);
 
 /* ---- stream analysis: what a .flac holds, frame by frame (flac-py README, known issue 3) -- */
 /* The reference has no such tool ("It would be nice to have a tool providing information
