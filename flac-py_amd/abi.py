@@ -278,6 +278,34 @@ class StreamResult(C.Structure):
     ]
 
 
+class BatchStreamResult(C.Structure):
+    _fields_ = [
+        ("frames", C.c_int64),
+        ("samples", C.c_int64),
+        ("consumed", C.c_int64),
+        ("status", C.c_int32),
+        ("site", C.c_int32),
+        ("probes", C.c_int64),
+        ("pass2_frames", C.c_int64),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
+class BatchSummary(C.Structure):
+    _fields_ = [
+        ("candidates", C.c_int64),
+        ("frames", C.c_int64),
+        ("max_samples", C.c_int64),
+        ("probes", C.c_int64),
+        ("pass2_frames", C.c_int64),
+        ("reserved", C.c_int64 * 3),
+    ]
+
+
+PLANAR_INT16, PLANAR_INT32, PLANAR_FLOAT32 = 0, 1, 2  # flacmi_planar_elem
+PLANAR_ELEM = {"int16": PLANAR_INT16, "int32": PLANAR_INT32, "float32": PLANAR_FLOAT32}
+
+
 class RecompressResult(C.Structure):
     _fields_ = [
         ("frames", C.c_int64),
@@ -419,6 +447,12 @@ SIGNATURES = {
     "flacmi_units_out_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "flacmi_planar_out_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "flacmi_decode_batch_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(DecodeParams),
+                                           C.c_int32, C.c_void_p, C.POINTER(BatchSummary)]),
+    "flacmi_decode_batch_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p]),
     "flacmi_recompress_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(DecodeParams),
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Params),
                                          C.POINTER(FrameParams), C.POINTER(RecompressResult)]),

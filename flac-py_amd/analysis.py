@@ -524,6 +524,72 @@ class Analyzer:
         return (buf.cpu().numpy().view(dt), guard, stride, st.cpu().numpy()[:len(frames)],
                 int(w.cpu().numpy().view(np.uint32)[0]))
 
+    def planar_out(self, streams, channels: int, elem: str, sample_size: int = 16, pitch: int = 0, lengths=None,
+                   guard: int = 64, fill: int = 0x5A):
+        """flacmi_planar_out_device alone.  streams: per stream a list of (int32 array [channels][block_size],
+        row pitch) in stream order, each frame placed on the device at its own pitch; elem "int16" | "int32" |
+        "float32"; pitch in elements (0: the longest stream, rounded up to 16 bytes); lengths: optional cut per
+        stream.  The rows lie between two guard regions of `guard` elements and every byte of the buffer is
+        `fill` beforehand.  -> (the whole buffer as a 1-D array of the element type, the index of row 0's first
+        element in it, the pitch, status per frame in list order)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        dt = {"int16": np.int16, "int32": np.int32, "float32": np.float32}[elem]
+        sb = np.dtype(dt).itemsize
+        g = 16 // sb
+        keep, recs = [], []
+        longest = 0
+        for si, frames in enumerate(streams):
+            first = 0
+            for x, fp in frames:
+                x = np.asarray(x, dtype=np.int32).reshape(channels, -1)
+                bs = x.shape[1]
+                rows = np.full((channels, fp), 0x7BADBAD, dtype=np.int32)  # what lies past a frame's length
+                rows[:, :bs] = x
+                r = torch.from_numpy(rows).to(dev)
+                keep.append(r)
+                recs.append((r.data_ptr(), fp, first, bs, si))
+                first += bs
+            longest = max(longest, first)
+        pitch = pitch or max(g, (longest + g - 1) // g * g)
+        t = np.array(recs, dtype=abi.PCM_FRAME_DTYPE) if recs else np.zeros(0, dtype=abi.PCM_FRAME_DTYPE)
+        tab = torch.from_numpy(t.view(np.uint8).copy()).to(dev) if recs else None
+        guard = (guard + g - 1) // g * g
+        n_rows = len(streams) * channels
+        buf = torch.from_numpy(np.full((2 * guard + max(n_rows, 1) * pitch) * sb, fill, dtype=np.uint8)).to(dev)
+        st = torch.full((max(len(recs), 1),), -1, dtype=torch.int32, device=dev)
+        ln = torch.from_numpy(np.asarray(lengths, dtype=np.int64)).to(dev) if lengths is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self.lib.flacmi_planar_out_device(self.ctx, tab.data_ptr() if recs else None, len(recs), len(streams), channels,
+                                                ln.data_ptr() if ln is not None else None, sample_size,
+                                                abi.PLANAR_ELEM[elem], buf.data_ptr() + guard * sb, pitch, st.data_ptr(),
+                                                stream), "flacmi_planar_out_device")
+        torch.cuda.synchronize(dev)
+        return buf.cpu().numpy().view(dt), guard, pitch, st.cpu().numpy()[:len(recs)]
+
+    def decode_batch(self, data_ptr: int, seg_offsets: np.ndarray, channels: int, sample_size: int, check_crc: bool,
+                     max_block_size: int, spec_wasted_bits: bool = False):
+        """flacmi_decode_batch_host: the frame regions of len(seg_offsets) - 1 whole streams, packed back to
+        back in host memory at data_ptr -> (BatchStreamResult array, BatchSummary).  The frame list stays in the
+        context for batch_fetch."""
+        seg = np.ascontiguousarray(seg_offsets, dtype=np.int64)
+        n = len(seg) - 1
+        dp = abi.DecodeParams()
+        dp.channels, dp.sample_size, dp.first_frame, dp.check_crc = channels, sample_size, -1, int(check_crc)
+        dp.reserved0 = abi.DECODE_WASTED_SPEC if spec_wasted_bits else 0
+        res = (abi.BatchStreamResult * max(n, 1))()
+        summary = abi.BatchSummary()
+        check(self.lib.flacmi_decode_batch_host(self.ctx, data_ptr, seg.ctypes.data, n, C.byref(dp), max_block_size,
+                                                C.cast(res, C.c_void_p), C.byref(summary)), "flacmi_decode_batch_host")
+        return res, summary
+
+    def batch_fetch(self, out_ptr: int, pitch: int, elem: str, res, host: bool = False, stream: int = 0):
+        """flacmi_decode_batch_fetch: the kept frame list as [streams][channels][pitch] rows of `elem` at
+        out_ptr (device memory, written on `stream`; host memory with host=True); `res` receives the final
+        per-stream results (int16: a range finding stops its stream)."""
+        check(self.lib.flacmi_decode_batch_fetch(self.ctx, out_ptr, pitch, abi.PLANAR_ELEM[elem], int(host),
+                                                 C.cast(res, C.c_void_p), stream), "flacmi_decode_batch_fetch")
+
     def recompress_chunk(self, data_ptr: int, nbytes: int, first_byte: int, channels: int, sample_size: int,
                          check_crc: bool, max_block_size: int, final_chunk: bool, restart: bool, block_len: int,
                          params: abi.Params, fp: abi.FrameParams, spec_wasted_bits: bool = False, out_alloc=None):

@@ -17,6 +17,17 @@ packed on the device (decoder.decode_wav over flacmi_decode_stream_host) and wri
 the wave module as the reference does; --check-crc also verifies CRC-8 / CRC-16, which the
 reference reads unchecked.
 
+    python -m flac_amd decode-many --out-dir DIR in1.flac in2.flac ... [--device N] [--check-crc] [--spec-wasted-bits]
+
+decode-many (flac_amd.batch over flacmi_decode_batch_host): the inputs grouped by (channels, sample
+size) and each group decoded in one device call into planar rows; one DIR/<input name>.wav per
+input, byte-identical to what decode writes for that file.  Where a stream stops, its WAV holds the
+frames before the stop, a `stopped` line on stderr names the file and the exception, the other
+streams go on, and the exit status is 1.  16-bit groups come back as range-checked int16 rows; every
+other sample size as int32 rows packed on the host, and a file of those that holds a sample outside
+its width (to_bytes raises OverflowError) is decoded a second time alone through decode's path, whose
+PCM kernel stops it at that frame.
+
     python -m flac_amd recompress infile.flac outfile.flac [-b N] [-l N] [-q N] [-r [M,]N]
                                                             [--fixed-only] [--fallback] [--stereo] [--lpc-sign]
                                                             [--wasted-bits] [--rice-search] [--size-choice]
@@ -97,6 +108,13 @@ def make_argument_parser():
     dec.add_argument("--spec-wasted-bits", action="store_true",
                      help="read a subframe's wasted bits as the format codes them and shift them back in (the "
                           "reference reads one too few and leaves the samples unshifted)")
+    many = action.add_parser("decode-many", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    many.add_argument("infiles", type=Path, nargs="+", metavar="in.flac")
+    many.add_argument("--out-dir", type=Path, required=True, metavar="DIR")
+    many.add_argument("--device", type=int, default=0)
+    many.add_argument("--check-crc", action="store_true", help="verify the frames' CRC-8 and CRC-16")
+    many.add_argument("--spec-wasted-bits", action="store_true",
+                      help="read wasted bits as the format codes them and shift them back in")
     rec = action.add_parser("recompress", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     rec.add_argument("infile", type=Path, metavar="infile.flac")
     rec.add_argument("outfile", type=Path, metavar="outfile.flac")
@@ -179,6 +197,59 @@ def cmd_decode(args) -> None:
     print(f"Decoding completed in {seconds:.6g} seconds")
 
 
+def cmd_decode_many(args) -> int:
+    from wave import open as wave_open
+
+    import numpy as np
+
+    from . import batch
+    from .decoder import decode_pcm
+    names = [p.with_suffix(".wav").name for p in args.infiles]
+    if len(set(names)) != len(names):
+        raise SystemExit("decode-many: two inputs would write the same file in --out-dir")
+    args.out_dir.mkdir(parents=True, exist_ok=True)
+    t0 = timer()
+    results = batch.decode_files(args.infiles, dtype="auto", device=args.device, check_crc=args.check_crc,
+                                 spec_wasted_bits=args.spec_wasted_bits)
+    failed = 0
+    for path, name, r in zip(args.infiles, names, results):
+        error = r.error
+        if r.data is None or r.sample_size % 8:
+            # Python's wave module doesn't handle sample sizes that are not multiple of a byte.
+            error = error or AssertionError(f"sample size {r.sample_size}")
+            pcm = None
+        else:
+            B = r.sample_size // 8
+            x = r.data[:, :r.length].cpu().numpy().T  # [length][channels]: decoder.py:52 zip(*samples)
+            if B == 2:
+                pcm = np.ascontiguousarray(x, dtype="<i2").tobytes()
+            else:
+                if B < 4 and x.size and (x.min() < -(1 << (8 * B - 1)) or x.max() >= 1 << (8 * B - 1)):
+                    # to_bytes raises OverflowError: the stream alone, whose PCM kernel stops at that frame
+                    pcm, error = b"", None
+                    try:
+                        for bs in decode_pcm(path, device=args.device, check_crc=args.check_crc,
+                                             spec_wasted_bits=args.spec_wasted_bits)[4]:
+                            pcm += bs
+                    except Exception as e:  # noqa: BLE001
+                        error = e
+                else:
+                    pcm = np.ascontiguousarray(x, dtype="<i4").view(np.uint8).reshape(-1, 4)[:, :B].tobytes()
+        if pcm is not None:
+            info = r.streaminfo
+            with wave_open(str(args.out_dir / name), mode="wb") as w:
+                w.setframerate(info.sample_rate)
+                w.setsampwidth(info.sample_size // 8)
+                w.setnchannels(info.channels)
+                w.setnframes(info.samples)
+                w.writeframes(pcm)
+        if error is not None:
+            failed += 1
+            print(f"stopped\tfile={path}\texception={type(error).__name__}\tmessage={error}", file=sys.stderr)
+    print(f"Decoding of {len(results)} streams completed in {timer() - t0:.6g} seconds, {failed} stopped")
+    return 1 if failed else 0
+
+
 def cmd_recompress(args) -> int:
     from .encoder import EncoderParameters
     from .recompress import recompress
@@ -222,6 +293,8 @@ def main(argv=None) -> int:
         cmd_encode(args)
     if args.action == "decode":
         cmd_decode(args)
+    if args.action == "decode-many":
+        return cmd_decode_many(args)
     if args.action == "recompress":
         return cmd_recompress(args)
     if args.action == "analyze":

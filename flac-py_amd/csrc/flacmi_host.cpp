@@ -190,8 +190,10 @@ struct flacmi_ctx {
     hipEvent_t lpc_done[kMaxChunks] = {}; /* k_lpc of chunk i finished (no timing) */
     int ncalls = 0; /* calls since the last timing reset */
     struct EncState* enc = nullptr; /* flacmi_encode_pipeline's streams, slots and pinned arrays */
+    struct BatchState* batch = nullptr; /* flacmi_decode_batch_host's kept frame list */
 };
 static void enc_free(struct EncState* es);
+static void batch_free(struct BatchState* bs);
 static int enc_streams(flacmi_ctx* ctx);
 static hipStream_t enc_side(flacmi_ctx* ctx);
 
@@ -326,6 +328,7 @@ void flacmi_destroy(flacmi_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     enc_free(ctx->enc);
+    batch_free(ctx->batch);
     for (auto& kv : ctx->windows) (void)hipFree(kv.second);
     for (auto& kv : ctx->chunk_weights) (void)hipFree(kv.second);
     for (DevBuf* b : {&ctx->bound, &ctx->idx, &ctx->sd_data, &ctx->sd_table, &ctx->sd_meta, &ctx->sd_rows, &ctx->sd_pcm, &ctx->si_frames, &ctx->si_subs, &ctx->si_parts, &ctx->slow, &ctx->dec, &ctx->rec, &ctx->retry, &ctx->h_samples, &ctx->h_meta, &ctx->h_params, &ctx->h_residual, &ctx->h_acf,
@@ -1235,7 +1238,7 @@ static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64
                               const int64_t* frame_offsets, int64_t n_frames, const flacmi_decode_params* dp,
                               const flacmi_batch* expect, int32_t* samples_out, int64_t out_stride,
                               int32_t* frame_status, int64_t* frame_mismatch, int64_t* frame_end, bool general,
-                              void* stream);
+                              void* stream, const int64_t* frame_limit = nullptr);
 
 int flacmi_decode_frames_end_device(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
                                     const int64_t* frame_offsets, int64_t n_frames,
@@ -1246,12 +1249,13 @@ int flacmi_decode_frames_end_device(flacmi_ctx* ctx, const uint8_t* stream_data,
                               out_stride, frame_status, frame_mismatch, frame_end, false, stream);
 }
 
-/* general: every frame through the general decoder kernel, as knob FLACMI_DECODE_GENERIC */
+/* general: every frame through the general decoder kernel, as knob FLACMI_DECODE_GENERIC;
+ * frame_limit (device, [n_frames], the batch decoder): the end of each frame's own stream */
 static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64_t stream_bytes,
                               const int64_t* frame_offsets, int64_t n_frames, const flacmi_decode_params* dp,
                               const flacmi_batch* expect, int32_t* samples_out, int64_t out_stride,
                               int32_t* frame_status, int64_t* frame_mismatch, int64_t* frame_end, bool general,
-                              void* stream) {
+                              void* stream, const int64_t* frame_limit) {
     if (!ctx || !dp) return fail(FLACMI_E_INVALID, "null argument");
     if (n_frames < 0 || stream_bytes < 0) return fail(FLACMI_E_INVALID, "negative size");
     if (n_frames == 0) return 0;
@@ -1307,6 +1311,7 @@ static int decode_frames_impl(flacmi_ctx* ctx, const uint8_t* stream_data, int64
     a.defer_all = general || knob(kKnobDecodeGeneric) != 0;
     a.crc_slice = ctx->d_crc;
     a.frame_end = frame_end;
+    a.frame_limit = frame_limit;
     HIP_TRY(launch_decode(a, (hipStream_t)stream));
     return 0;
 }
@@ -1410,6 +1415,40 @@ int flacmi_units_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int
     return 0;
 }
 
+int flacmi_planar_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64_t n_frames, int64_t n_streams,
+                             int32_t channels, const int64_t* lengths, int32_t sample_size, int32_t elem, void* out,
+                             int64_t pitch, int32_t* frame_status, void* stream) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null argument");
+    if (n_frames < 0 || n_streams < 0 || pitch < 0) return fail(FLACMI_E_INVALID, "negative size");
+    if (channels < 1 || channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (elem != FLACMI_PLANAR_INT16 && elem != FLACMI_PLANAR_INT32 && elem != FLACMI_PLANAR_FLOAT32)
+        return fail(FLACMI_E_INVALID, "elem must be a flacmi_planar_elem");
+    if (sample_size < 4 || sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    const int sb = elem == FLACMI_PLANAR_INT16 ? 2 : 4;
+    if ((pitch * sb) % 16 != 0) return fail(FLACMI_E_INVALID, "pitch must be a multiple of 16 bytes");
+    if (n_frames > 0 && (!frames || !frame_status)) return fail(FLACMI_E_INVALID, "null buffer");
+    if (((uintptr_t)frames & 7) != 0 || ((uintptr_t)out & 15) != 0 || ((uintptr_t)frame_status & 3) != 0 || ((uintptr_t)lengths & 7) != 0)
+        return fail(FLACMI_E_INVALID, "out must be 16-byte aligned, frames and lengths 8-byte, frame_status 4-byte");
+    if (n_frames > 0x7FFFFFFF || n_streams > 0x7FFFFFFF) return fail(FLACMI_E_UNSUPPORTED, "more than 2^31 - 1 frames or streams in one call");
+    if (n_streams == 0 || pitch == 0) return 0;
+    if (!out) return fail(FLACMI_E_INVALID, "null out");
+    const int64_t per = 256 * (16 / sb), tiles = (pitch + per - 1) / per;
+    if (tiles > 0x7FFFFFFF / (n_streams * channels)) return fail(FLACMI_E_UNSUPPORTED, "more than 2^31 - 1 workgroups: pass fewer streams");
+    if (int rc = set_device(ctx)) return rc;
+    PlanarArgs a{};
+    a.frames = frames;
+    a.n_frames = n_frames;
+    a.n_streams = n_streams;
+    a.channels = channels;
+    a.sample_size = sample_size;
+    a.lengths = lengths;
+    a.out = out;
+    a.pitch = pitch;
+    a.status = frame_status;
+    HIP_TRY(launch_planar(a, elem, (hipStream_t)stream));
+    return 0;
+}
+
 static inline bool walk_ref_error(int32_t st) { return st != 0 && (st & 0xFFFF) != FLACMI_STATUS_VERIFY; }
 
 int flacmi_host_chain_walk(const flacmi_frame_candidate* table, int64_t n_candidates, const int32_t* status,
@@ -1510,24 +1549,41 @@ struct ScopedDev { /* device scratch of one flacmi_decode_stream_host call */
 /* Steps 1 to 5 of flacmi_decode_stream_host (copy in, index, pass 1, the chain walk with its
  * probes, pass 2), shared with flacmi_recompress_host: the chain's first nc frames are decoded,
  * frame i's rows are pass 2's (row2[i] >= 0: rows2 at stride2) or pass 1's (its candidate's, in
- * ctx->sd_rows at stride1); stop is the status word of the frame at pos, or 0. */
+ * ctx->sd_rows at stride1); stop is the status word of the frame at pos, or 0.
+ *
+ * flacmi_decode_batch_host runs the same steps once over many whole streams packed back to
+ * back (seg[0 .. nseg] their bounds): every stream's first byte joins the candidates, so no
+ * proposed end lies past the frame's own stream; the walk runs once per stream over its slice of
+ * the table and leaves stream s's frames in chain[segs[s].c0 ..) with its own nc, stop and pos;
+ * the general decoder gets each frame's stream end (DecodeArgs.frame_limit).  Without seg the
+ * launches are the single stream's, in its order. */
 namespace {
 struct StreamFrames {
+    struct Seg {
+        int64_t c0 = 0, nc = 0, pos = 0, probes = 0, n2 = 0;
+        int32_t stop = 0;
+    };
     std::vector<flacmi_chain_frame> chain;
     std::vector<int32_t> bsz;
     std::vector<int64_t> row2;
+    std::vector<Seg> segs; /* the batch decoder's streams */
     ScopedDev rows2;
     int64_t nc = 0, n2 = 0, stride1 = 4, stride2 = 4, pos = 0, candidates = 0, probes = 0;
     int32_t stop = 0;
 };
 }  // namespace
 
+static void batch_invalidate(flacmi_ctx* ctx);
+
 static int stream_frames(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, int64_t first_byte,
-                         const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk, StreamFrames& h) {
+                         const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk, StreamFrames& h,
+                         const int64_t* seg = nullptr, int64_t nseg = 0) {
     hipStream_t s = ctx->stream;
     const int ch = dp->channels;
+    const bool batch = seg != nullptr;
     flacmi_decode_params p1 = *dp;
     p1.first_frame = -1;
+    batch_invalidate(ctx); /* a kept frame list points into the buffers this call reuses */
 
     /* 1. the chunk, 2. the index */
     if (int rc = ensure_buf(ctx->sd_data, (size_t)bytes + 32)) return rc;
@@ -1549,6 +1605,39 @@ static int stream_frames(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, in
     std::vector<flacmi_frame_candidate> table((size_t)n);
     if (n) HIP_TRY(hipMemcpy(table.data(), (char*)ctx->sd_table.p + 16, sizeof(flacmi_frame_candidate) * (size_t)n, hipMemcpyDeviceToHost));
 
+    /* the batch: every stream's first byte is a candidate, listed or not; seg_k[s] is the table
+     * index of stream s's first candidate, lim[k] the end of candidate k's stream */
+    std::vector<int64_t> seg_k, lim;
+    if (batch) {
+        std::vector<flacmi_frame_candidate> merged;
+        merged.reserve((size_t)(n + nseg));
+        seg_k.assign((size_t)nseg + 1, 0);
+        int64_t k = 0;
+        for (int64_t g = 0; g < nseg; ++g) {
+            const int64_t b = seg[g], e = seg[g + 1];
+            seg_k[(size_t)g] = (int64_t)merged.size();
+            if (b == e) continue;
+            if (!(k < n && table[(size_t)k].offset == b)) {
+                flacmi_frame_candidate c{};
+                if (e - b >= 2 && data[b] == 0xFF && (data[b + 1] & 0xFE) == 0xF8 && parse_header(data + b, e - b, 0, false, c)) {
+                    const int32_t bs = c.block_size;
+                    c = flacmi_frame_candidate{};
+                    c.block_size = bs;
+                }
+                c.offset = b;
+                merged.push_back(c);
+                lim.push_back(e);
+            }
+            for (; k < n && table[(size_t)k].offset < e; ++k) {
+                merged.push_back(table[(size_t)k]);
+                lim.push_back(e);
+            }
+        }
+        seg_k[(size_t)nseg] = (int64_t)merged.size();
+        table.swap(merged);
+        n = (int64_t)table.size();
+    }
+
     /* 3. pass 1: every candidate, proposed to end at the next one */
     int64_t stride1 = max_block_size;
     if (stride1 == 0)
@@ -1559,87 +1648,111 @@ static int stream_frames(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, in
         return fail(FLACMI_E_UNSUPPORTED, "%lld candidates of %lld-sample rows exceed 4 GiB: pass a smaller chunk", (long long)n, (long long)stride1);
     std::vector<int32_t> st1((size_t)n);
     std::vector<int64_t> end1((size_t)n);
-    /* per-frame words: offsets [n + 1] i64, ends [n] i64, mismatches [n] i64, status [n] i32 */
-    if (int rc = ensure_buf(ctx->sd_meta, 28 * (size_t)n + 64)) return rc;
+    /* per-frame words: offsets [n + 1] i64, ends [n] i64, mismatches [n] i64, stream ends [n] i64 (the
+     * batch), status [n] i32 */
+    if (int rc = ensure_buf(ctx->sd_meta, 36 * (size_t)n + 64)) return rc;
     int64_t* d_off = (int64_t*)ctx->sd_meta.p;
     int64_t* d_end = d_off + n + 1;
     int64_t* d_mm = d_end + n;
-    int32_t* d_st = (int32_t*)(d_mm + n);
+    int64_t* d_lim = d_mm + n;
+    int32_t* d_st = (int32_t*)(d_lim + n);
     if (n) {
         std::vector<int64_t> off((size_t)n + 1);
         for (int64_t k = 0; k < n; ++k) off[k] = table[k].offset;
         off[n] = bytes;
         if (int rc = ensure_buf(ctx->sd_rows, rows1)) return rc;
         HIP_TRY(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-        if (int rc = flacmi_decode_frames_end_device(ctx, d_data, bytes, d_off, n, &p1, nullptr, (int32_t*)ctx->sd_rows.p, stride1,
-                                                     d_st, d_mm, d_end, s))
+        if (batch) HIP_TRY(hipMemcpyAsync(d_lim, lim.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        if (int rc = decode_frames_impl(ctx, d_data, bytes, d_off, n, &p1, nullptr, (int32_t*)ctx->sd_rows.p, stride1, d_st, d_mm,
+                                        d_end, false, s, batch ? d_lim : nullptr))
             return rc;
         HIP_TRY(hipMemcpyAsync(st1.data(), d_st, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(end1.data(), d_end, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
 
-    /* 4. the walk; a probe decodes the one frame at w.pos into rows of the largest block */
+    /* 4. the walk, once per stream; a probe decodes the one frame at w.pos into rows of the largest block */
     std::vector<flacmi_chain_frame>& chain = h.chain;
     chain.assign((size_t)n + 16, flacmi_chain_frame{});
-    flacmi_walk w{};
-    w.pos = first_byte;
+    std::vector<StreamFrames::Seg>& segs = h.segs;
+    const int64_t one[2] = {first_byte, bytes};
+    if (!batch) seg = one, nseg = 1;
+    segs.assign((size_t)nseg, StreamFrames::Seg{});
     ScopedDev probe_rows, probe_meta;
     constexpr int64_t kProbeStride = 65536;
-    for (;;) {
-        if (int rc = flacmi_host_chain_walk(table.data(), n, st1.data(), end1.data(), bytes, final_chunk, &w, chain.data(),
-                                            (int64_t)chain.size()))
-            return rc;
-        if (w.state == FLACMI_WALK_FULL) {
-            chain.resize(chain.size() * 2);
-            w.state = FLACMI_WALK_RUN;
-            continue;
+    int64_t total = 0; /* chain frames of the streams before */
+    for (int64_t g = 0; g < nseg; ++g) {
+        StreamFrames::Seg& sg = segs[(size_t)g];
+        const int64_t k0 = batch ? seg_k[(size_t)g] : 0, k1 = batch ? seg_k[(size_t)g + 1] : n, send = seg[g + 1];
+        flacmi_walk w{};
+        w.pos = seg[g];
+        sg.c0 = total;
+        for (;;) {
+            if ((int64_t)chain.size() < total + 16) chain.resize(2 * chain.size() + 16);
+            if (int rc = flacmi_host_chain_walk(table.data() + k0, k1 - k0, st1.data() + k0, end1.data() + k0, send, final_chunk, &w,
+                                                chain.data() + total, (int64_t)chain.size() - total))
+                return rc;
+            if (w.state == FLACMI_WALK_FULL) {
+                chain.resize(chain.size() * 2);
+                w.state = FLACMI_WALK_RUN;
+                continue;
+            }
+            if (w.state != FLACMI_WALK_PROBE) break;
+            if ((int64_t)chain.size() - total == w.n_chain) chain.resize(chain.size() * 2);
+            if (!probe_rows.p) {
+                if (int rc = probe_rows.alloc(sizeof(int32_t) * (size_t)ch * kProbeStride)) return rc;
+                if (int rc = probe_meta.alloc(64)) return rc;
+            }
+            int64_t* q_off = (int64_t*)probe_meta.p; /* offsets [2], end, mismatch, status */
+            const int64_t off2[2] = {w.pos, send};
+            HIP_TRY(hipMemcpyAsync(q_off, off2, sizeof(off2), hipMemcpyHostToDevice, s));
+            int32_t k1s = 0;
+            HIP_TRY(hipStreamSynchronize(s)); /* off2 is a stack array */
+            /* FLACMI_DECODE_GENERIC semantics: the general decoder alone (the batch: the proposed end is
+             * the stream's end, the frame's limit) */
+            if (int rc = decode_frames_impl(ctx, d_data, bytes, q_off, 1, &p1, nullptr, (int32_t*)probe_rows.p, kProbeStride,
+                                            (int32_t*)(q_off + 4), q_off + 3, q_off + 2, true, s, batch ? q_off + 1 : nullptr))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(&k1s, q_off + 4, sizeof(k1s), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&w.probe_end, q_off + 2, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            w.probe_status = k1s;
+            /* the proposed end was the chunk's: ending anywhere before it is no finding yet */
+            if (!walk_ref_error(k1s) && (k1s >> 16) == FLACMI_DSITE_FRAME_END) w.probe_status = 0;
+            ++sg.probes;
         }
-        if (w.state != FLACMI_WALK_PROBE) break;
-        if ((int64_t)chain.size() == w.n_chain) chain.resize(chain.size() * 2);
-        if (!probe_rows.p) {
-            if (int rc = probe_rows.alloc(sizeof(int32_t) * (size_t)ch * kProbeStride)) return rc;
-            if (int rc = probe_meta.alloc(64)) return rc;
-        }
-        int64_t* q_off = (int64_t*)probe_meta.p; /* offsets [2], end, mismatch, status */
-        const int64_t off2[2] = {w.pos, bytes};
-        HIP_TRY(hipMemcpyAsync(q_off, off2, sizeof(off2), hipMemcpyHostToDevice, s));
-        int32_t k1 = 0;
-        HIP_TRY(hipStreamSynchronize(s)); /* off2 is a stack array */
-        /* FLACMI_DECODE_GENERIC semantics: the general decoder alone */
-        if (int rc = decode_frames_impl(ctx, d_data, bytes, q_off, 1, &p1, nullptr, (int32_t*)probe_rows.p, kProbeStride,
-                                        (int32_t*)(q_off + 4), q_off + 3, q_off + 2, true, s))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(&k1, q_off + 4, sizeof(k1), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&w.probe_end, q_off + 2, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        w.probe_status = k1;
-        /* the proposed end was the chunk's: ending anywhere before it is no finding yet */
-        if (!walk_ref_error(k1) && (k1 >> 16) == FLACMI_DSITE_FRAME_END) w.probe_status = 0;
-        ++h.probes;
+        sg.nc = w.n_chain;
+        sg.stop = w.state == FLACMI_WALK_STOPPED ? w.stop_status : 0;
+        sg.pos = w.pos;
+        for (int64_t i = 0; i < sg.nc; ++i)
+            if (chain[(size_t)(total + i)].candidate >= 0) chain[(size_t)(total + i)].candidate += k0;
+        total += sg.nc;
+        h.probes += sg.probes;
     }
-    int64_t nc = w.n_chain;
-    int32_t stop = w.state == FLACMI_WALK_STOPPED ? w.stop_status : 0;
 
     /* block sizes; 5. pass 2: the chain frames whose pass-1 rows are not final, in runs of
      * neighbours, with the chain's own offsets */
     std::vector<int32_t>& bsz = h.bsz;
     std::vector<int64_t>& row2 = h.row2; /* index among the pass-2 frames */
-    bsz.assign((size_t)nc, 0);
-    row2.assign((size_t)nc, -1);
+    bsz.assign((size_t)total, 0);
+    row2.assign((size_t)total, -1);
     int64_t n2 = 0, stride2 = 4;
-    for (int64_t i = 0; i < nc; ++i) {
-        const flacmi_chain_frame& c = chain[i];
-        if (c.candidate >= 0) {
-            bsz[i] = table[c.candidate].block_size;
-        } else {
-            flacmi_frame_candidate h{};
-            if (!parse_header(data, bytes, c.offset, false, h)) return fail(FLACMI_E_INVALID, "internal: chain frame without a header");
-            bsz[i] = h.block_size;
-        }
-        if (c.status != 0) {
-            row2[i] = n2++;
-            stride2 = std::max<int64_t>(stride2, (bsz[i] + 3) & ~3);
+    for (int64_t g = 0; g < nseg; ++g) {
+        StreamFrames::Seg& sg = segs[(size_t)g];
+        for (int64_t i = sg.c0; i < sg.c0 + sg.nc; ++i) {
+            const flacmi_chain_frame& c = chain[i];
+            if (c.candidate >= 0 && table[c.candidate].block_size > 0) {
+                bsz[i] = table[c.candidate].block_size;
+            } else {
+                flacmi_frame_candidate h{};
+                if (!parse_header(data, seg[g + 1], c.offset, false, h)) return fail(FLACMI_E_INVALID, "internal: chain frame without a header");
+                bsz[i] = h.block_size;
+            }
+            if (c.status != 0) {
+                row2[i] = n2++;
+                ++sg.n2;
+                stride2 = std::max<int64_t>(stride2, (bsz[i] + 3) & ~3);
+            }
         }
     }
     h.n2 = n2;
@@ -1647,49 +1760,59 @@ static int stream_frames(flacmi_ctx* ctx, const uint8_t* data, int64_t bytes, in
     ScopedDev meta2;
     if (n2) {
         if (int rc = rows2.alloc(sizeof(int32_t) * (size_t)n2 * ch * (size_t)stride2)) return rc;
-        if (int rc = meta2.alloc(32 * (size_t)n2 + 64)) return rc;
-        int64_t* e_off = (int64_t*)meta2.p; /* offsets [2 n2] (a run of r frames uses r + 1), mismatch [n2], status [n2] */
+        if (int rc = meta2.alloc(40 * (size_t)n2 + 64)) return rc;
+        /* offsets [2 n2] (a run of r frames uses r + 1), mismatch [n2], stream ends [n2] (the batch), status [n2] */
+        int64_t* e_off = (int64_t*)meta2.p;
         int64_t* e_mm = e_off + 2 * n2;
-        int32_t* e_st = (int32_t*)(e_mm + n2);
-        std::vector<int64_t> off;
+        int64_t* e_lim = e_mm + n2;
+        int32_t* e_st = (int32_t*)(e_lim + n2);
+        std::vector<int64_t> off, lim2;
         std::vector<int32_t> st2((size_t)n2);
         struct Run { int64_t first2, count, off0; };
         std::vector<Run> runs;
-        for (int64_t i = 0; i < nc;) {
-            if (row2[i] < 0) { ++i; continue; }
-            int64_t j = i;
-            const int64_t o0 = (int64_t)off.size();
-            while (j < nc && row2[j] >= 0) off.push_back(chain[j++].offset);
-            off.push_back(chain[j - 1].end);
-            runs.push_back({row2[i], j - i, o0});
-            i = j;
+        for (int64_t g = 0; g < nseg; ++g) { /* a run lies inside one stream */
+            const int64_t c1 = segs[(size_t)g].c0 + segs[(size_t)g].nc;
+            for (int64_t i = segs[(size_t)g].c0; i < c1;) {
+                if (row2[i] < 0) { ++i; continue; }
+                int64_t j = i;
+                const int64_t o0 = (int64_t)off.size();
+                while (j < c1 && row2[j] >= 0) off.push_back(chain[j++].offset);
+                off.push_back(chain[j - 1].end);
+                runs.push_back({row2[i], j - i, o0});
+                lim2.insert(lim2.end(), (size_t)(j - i), seg[g + 1]);
+                i = j;
+            }
         }
         /* off holds n2 + (number of runs) <= 2 n2 entries */
         HIP_TRY(hipMemcpyAsync(e_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, s));
+        if (batch) HIP_TRY(hipMemcpyAsync(e_lim, lim2.data(), sizeof(int64_t) * (size_t)n2, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (const Run& r : runs) {
-            if (int rc = flacmi_decode_frames_end_device(ctx, d_data, bytes, e_off + r.off0, r.count, &p1, nullptr,
-                                                         (int32_t*)rows2.p + r.first2 * ch * stride2, stride2, e_st + r.first2,
-                                                         e_mm + r.first2, nullptr, s))
+            if (int rc = decode_frames_impl(ctx, d_data, bytes, e_off + r.off0, r.count, &p1, nullptr,
+                                            (int32_t*)rows2.p + r.first2 * ch * stride2, stride2, e_st + r.first2, e_mm + r.first2,
+                                            nullptr, false, s, batch ? e_lim + r.first2 : nullptr))
                 return rc;
         }
         HIP_TRY(hipMemcpyAsync(st2.data(), e_st, sizeof(int32_t) * (size_t)n2, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        for (int64_t i = 0; i < nc; ++i) {
-            if (row2[i] >= 0 && st2[row2[i]] != 0) { /* final: the stream stops at this frame */
-                stop = st2[row2[i]];
-                nc = i;
-                w.pos = chain[i].offset;
-                break;
+        for (int64_t g = 0; g < nseg; ++g) {
+            StreamFrames::Seg& sg = segs[(size_t)g];
+            for (int64_t i = sg.c0; i < sg.c0 + sg.nc; ++i) {
+                if (row2[i] >= 0 && st2[row2[i]] != 0) { /* final: the stream stops at this frame */
+                    sg.stop = st2[row2[i]];
+                    sg.nc = i - sg.c0;
+                    sg.pos = chain[i].offset;
+                    break;
+                }
             }
         }
     }
 
-    h.nc = nc;
-    h.stop = stop;
+    h.nc = segs[0].nc; /* the single stream's */
+    h.stop = segs[0].stop;
+    h.pos = segs[0].pos;
     h.stride1 = stride1;
     h.stride2 = stride2;
-    h.pos = w.pos;
     return 0;
 }
 
@@ -1788,6 +1911,189 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
     res->consumed = w.pos;
     res->status = stop & 0xFFFF;
     res->site = (stop >> 16) & 0xFFFF;
+    return 0;
+}
+
+/* ---- batch decoder -------------------------------------------------------------------- */
+struct BatchState {
+    bool valid = false;
+    int32_t channels = 0, sample_size = 0;
+    int64_t n_streams = 0, n_frames = 0;
+    ScopedDev rows2;                    /* pass 2's rows (pass 1's are ctx->sd_rows) */
+    DevBuf list, out;                   /* device: frames [n_frames], lengths [n_streams] i64, the same after a fetch's range
+                                           findings, status [n_frames] i32; the host fetch's rows */
+    std::vector<flacmi_pcm_frame> pf;   /* ordered by (stream, first_sample) */
+    std::vector<int64_t> first;         /* [n_streams + 1]: stream s's frames are pf[first[s] .. first[s + 1]) */
+    std::vector<int64_t> offset;        /* [n_frames]: the frame's byte offset in data */
+    std::vector<flacmi_batch_stream_result> res;
+};
+static void batch_free(BatchState* bs) {
+    if (!bs) return;
+    if (bs->list.p) (void)hipFree(bs->list.p);
+    if (bs->out.p) (void)hipFree(bs->out.p);
+    delete bs;
+}
+static void batch_invalidate(flacmi_ctx* ctx) {
+    if (ctx->batch) ctx->batch->valid = false;
+}
+
+int flacmi_decode_batch_host(flacmi_ctx* ctx, const uint8_t* data, const int64_t* seg_offsets, int64_t n_streams,
+                             const flacmi_decode_params* dp, int32_t max_block_size, flacmi_batch_stream_result* results,
+                             flacmi_batch_summary* summary) {
+    if (!dp || !results || !summary || !seg_offsets) return fail(FLACMI_E_INVALID, "null argument");
+    if (n_streams < 1) return fail(FLACMI_E_INVALID, "n_streams must be at least 1");
+    if (seg_offsets[0] != 0) return fail(FLACMI_E_INVALID, "seg_offsets must start at 0");
+    for (int64_t g = 0; g < n_streams; ++g)
+        if (seg_offsets[g + 1] < seg_offsets[g]) return fail(FLACMI_E_INVALID, "seg_offsets descend at stream %lld", (long long)g);
+    if (n_streams > 0x7FFFFFFF) return fail(FLACMI_E_UNSUPPORTED, "more than 2^31 - 1 streams in one call");
+    const int64_t bytes = seg_offsets[n_streams];
+    if (bytes > 0 && !data) return fail(FLACMI_E_INVALID, "null buffer");
+    if (dp->channels < 1 || dp->channels > 8) return fail(FLACMI_E_INVALID, "channels must be 1..8");
+    if (dp->sample_size < 4 || dp->sample_size > 32) return fail(FLACMI_E_INVALID, "sample_size must be 4..32");
+    if (int rc = decode_flags_ok(dp)) return rc;
+    if (max_block_size < 0 || max_block_size > FLACMI_MAX_BLOCK + 1) return fail(FLACMI_E_INVALID, "max_block_size must be 0..65536");
+    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
+    memset(results, 0, sizeof(*results) * (size_t)n_streams);
+    memset(summary, 0, sizeof(*summary));
+    for (int64_t g = 0; g < n_streams; ++g) results[g].consumed = seg_offsets[g];
+    if (int rc = set_device(ctx)) return rc;
+    if (!ctx->batch) ctx->batch = new BatchState();
+    BatchState& b = *ctx->batch;
+    b.valid = false;
+    b.channels = dp->channels;
+    b.sample_size = dp->sample_size;
+    b.n_streams = n_streams;
+    b.n_frames = 0;
+    b.pf.clear();
+    b.offset.clear();
+    b.first.assign((size_t)n_streams + 1, 0);
+    b.res.assign(results, results + n_streams);
+    if (b.rows2.p) {
+        HIP_TRY(hipFree(b.rows2.p));
+        b.rows2.p = nullptr;
+    }
+    const int ch = dp->channels;
+    if (bytes > 0) {
+        StreamFrames h;
+        const int rc = stream_frames(ctx, data, bytes, 0, dp, max_block_size, 1, h, seg_offsets, n_streams);
+        summary->candidates = h.candidates;
+        summary->probes = h.probes;
+        summary->pass2_frames = h.n2;
+        if (rc) return rc;
+        std::swap(b.rows2.p, h.rows2.p);
+        for (int64_t g = 0; g < n_streams; ++g) {
+            const StreamFrames::Seg& sg = h.segs[(size_t)g];
+            flacmi_batch_stream_result& r = b.res[(size_t)g];
+            int64_t first = 0;
+            b.first[(size_t)g] = (int64_t)b.pf.size();
+            for (int64_t i = sg.c0; i < sg.c0 + sg.nc; ++i) {
+                flacmi_pcm_frame f{};
+                if (h.row2[i] >= 0) {
+                    f.rows = (int32_t*)b.rows2.p + h.row2[i] * ch * h.stride2;
+                    f.stride = h.stride2;
+                } else {
+                    f.rows = (int32_t*)ctx->sd_rows.p + h.chain[i].candidate * ch * h.stride1;
+                    f.stride = h.stride1;
+                }
+                f.first_sample = first;
+                f.block_size = h.bsz[i];
+                f.reserved0 = (int32_t)g;
+                first += h.bsz[i];
+                b.pf.push_back(f);
+                b.offset.push_back(h.chain[i].offset);
+            }
+            r.frames = sg.nc;
+            r.samples = first;
+            r.consumed = sg.pos;
+            r.status = sg.stop & 0xFFFF;
+            r.site = (sg.stop >> 16) & 0xFFFF;
+            r.probes = sg.probes;
+            r.pass2_frames = sg.n2;
+        }
+    }
+    b.first[(size_t)n_streams] = (int64_t)b.pf.size();
+    b.n_frames = (int64_t)b.pf.size();
+    /* the list on the device, with the streams' lengths and room for the status words */
+    const size_t nf = (size_t)b.n_frames;
+    if (int rc = ensure_buf(b.list, (sizeof(flacmi_pcm_frame) + 4) * nf + 16 * (size_t)n_streams + 16)) return rc;
+    hipStream_t s = ctx->stream;
+    if (nf) HIP_TRY(hipMemcpyAsync(b.list.p, b.pf.data(), sizeof(flacmi_pcm_frame) * nf, hipMemcpyHostToDevice, s));
+    std::vector<int64_t> len((size_t)n_streams);
+    for (int64_t g = 0; g < n_streams; ++g) {
+        len[(size_t)g] = b.res[(size_t)g].samples;
+        summary->frames += b.res[(size_t)g].frames;
+        summary->max_samples = std::max(summary->max_samples, b.res[(size_t)g].samples);
+    }
+    HIP_TRY(hipMemcpyAsync((char*)b.list.p + sizeof(flacmi_pcm_frame) * nf, len.data(), 8 * (size_t)n_streams, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(results, b.res.data(), sizeof(*results) * (size_t)n_streams);
+    b.valid = true;
+    return 0;
+}
+
+int flacmi_decode_batch_fetch(flacmi_ctx* ctx, void* out, int64_t pitch, int32_t elem, int32_t host_out,
+                              flacmi_batch_stream_result* results, void* stream) {
+    if (!ctx) return fail(FLACMI_E_INVALID, "null context");
+    if (!ctx->batch || !ctx->batch->valid)
+        return fail(FLACMI_E_INVALID, "no frame list: flacmi_decode_batch_host must be the context's last decode call");
+    BatchState& b = *ctx->batch;
+    if (elem != FLACMI_PLANAR_INT16 && elem != FLACMI_PLANAR_INT32 && elem != FLACMI_PLANAR_FLOAT32)
+        return fail(FLACMI_E_INVALID, "elem must be a flacmi_planar_elem");
+    const int sb = elem == FLACMI_PLANAR_INT16 ? 2 : 4;
+    int64_t longest = 0;
+    for (const auto& r : b.res) longest = std::max(longest, r.samples);
+    if (pitch < longest || (pitch * sb) % 16 != 0)
+        return fail(FLACMI_E_INVALID, "pitch must hold %lld samples and be a multiple of 16 bytes", (long long)longest);
+    if (pitch > 0 && !out) return fail(FLACMI_E_INVALID, "null out");
+    if (int rc = set_device(ctx)) return rc;
+    hipStream_t s = host_out ? ctx->stream : (hipStream_t)stream;
+    const size_t nf = (size_t)b.n_frames, total = (size_t)b.n_streams * b.channels * (size_t)pitch * sb;
+    void* d_out = out;
+    if (host_out) {
+        if (int rc = ensure_buf(b.out, total + 16)) return rc;
+        d_out = b.out.p;
+    }
+    const flacmi_pcm_frame* d_pf = (const flacmi_pcm_frame*)b.list.p;
+    int64_t* d_len = (int64_t*)((char*)b.list.p + sizeof(flacmi_pcm_frame) * nf);
+    int64_t* d_cut = d_len + b.n_streams;
+    int32_t* d_st = (int32_t*)(d_cut + b.n_streams);
+    std::vector<flacmi_batch_stream_result> res = b.res; /* the list stays whole for a later fetch of another type */
+    if (int rc = flacmi_planar_out_device(ctx, d_pf, b.n_frames, b.n_streams, b.channels, d_len, b.sample_size, elem, d_out, pitch,
+                                          d_st, s))
+        return rc;
+    if (elem == FLACMI_PLANAR_INT16 && nf > 0) { /* a range finding stops its stream at that frame */
+        std::vector<int32_t> st(nf);
+        HIP_TRY(hipMemcpyAsync(st.data(), d_st, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        bool again = false;
+        std::vector<int64_t> len((size_t)b.n_streams);
+        for (int64_t g = 0; g < b.n_streams; ++g) {
+            flacmi_batch_stream_result& r = res[(size_t)g];
+            for (int64_t i = b.first[(size_t)g]; i < b.first[(size_t)g] + r.frames; ++i) {
+                if (st[(size_t)i] == 0) continue;
+                r.frames = i - b.first[(size_t)g];
+                r.samples = b.pf[(size_t)i].first_sample;
+                r.consumed = b.offset[(size_t)i];
+                r.status = FLACMI_STATUS_OVERFLOW;
+                r.site = FLACMI_DSITE_PCM_RANGE;
+                again = true;
+                break;
+            }
+            len[(size_t)g] = r.samples;
+        }
+        if (again) { /* rare: the rows again, cut at the final lengths */
+            HIP_TRY(hipMemcpyAsync(d_cut, len.data(), 8 * (size_t)b.n_streams, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s)); /* len is a local */
+            if (int rc = flacmi_planar_out_device(ctx, d_pf, b.n_frames, b.n_streams, b.channels, d_cut, b.sample_size, elem, d_out,
+                                                  pitch, d_st, s))
+                return rc;
+        }
+    }
+    if (host_out && total > 0) {
+        HIP_TRY(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (results) memcpy(results, res.data(), sizeof(*results) * (size_t)b.n_streams);
     return 0;
 }
 

@@ -184,6 +184,8 @@ struct DecodeArgs {
     int64_t* frame_end;               /* optional [n_frames]: the byte after the frame's footer where the
                                          frame raised no reference exception, else -1 */
     int32_t wasted_spec;             /* FLACMI_DECODE_WASTED_SPEC: wasted bits = zeros + 1, shifted back in */
+    const int64_t* frame_limit;      /* optional [n_frames] (the batch decoder): the byte where frame f's own stream
+                                        ends inside the buffer; k_decode<END, true> raises EOFError there */
 };
 
 /* Frame index (k_index.hip): candidate frame starts of a byte stream, in stream order.  A tile
@@ -279,6 +281,20 @@ struct UnitsArgs {
     int64_t stride;          /* elements; a multiple of 16 bytes, >= block_len */
     int32_t* status;         /* [n_frames] */
     uint32_t* width;         /* one word: max over the samples written of x >= 0 ? x : ~x */
+};
+
+/* Planar rows from decoded frames (k_planar.hip): sample t of channel c of stream s goes to
+ * out[(s * channels + c) * pitch + t]; the frames are ordered by (stream, first_sample), the
+ * stream index in flacmi_pcm_frame.reserved0 */
+struct PlanarArgs {
+    const flacmi_pcm_frame* frames;
+    int64_t n_frames, n_streams;
+    int32_t channels, sample_size;
+    const int64_t* lengths;  /* optional [n_streams]: samples from lengths[s] on are written as 0 */
+    void* out;               /* int16, int32 or float rows, 16-byte aligned */
+    int64_t pitch;           /* elements; a multiple of 16 bytes */
+    int64_t tiles;           /* workgroups per row */
+    int32_t* status;         /* [n_frames] */
 };
 
 struct ResidLaunch {
@@ -403,6 +419,7 @@ int64_t index_scan_groups(int64_t n_tiles);
 hipError_t launch_pcm(const PcmArgs& a, hipStream_t s);
 /* clears a.status [n_frames] and a.width, then one workgroup per unit; sample_bytes 2 or 4 */
 hipError_t launch_units(const UnitsArgs& a, int32_t sample_bytes, hipStream_t s);
+hipError_t launch_planar(PlanarArgs a, int32_t elem, hipStream_t s);
 
 hipError_t launch_selftest(int32_t which, const double* x, double* out, int32_t* status, int64_t n,
                            const double* log2thr, hipStream_t s);

@@ -73,12 +73,15 @@ __device__ __forceinline__ int32_t expect_at(const DecodeArgs& a, int64_t u, int
 
 /* The general decoder: frame f, every check, the reference's exception precedence.  END: the
  * frame's end goes to a.frame_end (the stream decoder's first pass; the verifier's kernel is
- * built without the store). */
-template <bool END>
+ * built without the store).  SEG: the buffer holds many streams back to back (the batch decoder)
+ * and frame f's stream ends at byte a.frame_limit[f]: every read past it is the EOFError a read
+ * past stream_bytes is, whatever the next stream's bytes hold (each read is followed by a test of
+ * the position against end_bit before its value can decide anything but another such test). */
+template <bool END, bool SEG>
 __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*ring)[kDecThreads],
                              int16_t (*coef)[kDecThreads], const uint16_t* crct, const int lane) {
     const int64_t F = a.offsets[f], Fend = a.offsets[f + 1];
-    const int64_t end_bit = a.stream_bytes * 8; /* reading past it: EOFError */
+    const int64_t end_bit = (SEG ? a.frame_limit[f] : a.stream_bytes) * 8; /* reading past it: EOFError */
     int64_t bad = 0;
     int32_t st = 0;
     auto fail = [&](int32_t site) {
@@ -347,7 +350,7 @@ __device__ void decode_general(const DecodeArgs& a, const int64_t f, int32_t (*r
 }
 
 /* The frames k_decode_fx listed (a.defer_all: every frame), one lane each. */
-template <bool END>
+template <bool END, bool SEG>
 __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
     __shared__ int32_t ring[kRingSlots][kDecThreads];
     __shared__ int16_t coef[kRingSlots][kDecThreads]; /* precision <= 15 bits (4-bit field, 15 rejected) */
@@ -357,7 +360,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(DecodeArgs a) {
     __syncthreads();
     const int64_t nl = a.defer_all ? a.n_frames : (int64_t)*a.defer_count;
     for (int64_t k = (int64_t)blockIdx.x * kDecThreads + lane; k < nl; k += (int64_t)gridDim.x * kDecThreads)
-        decode_general<END>(a, a.defer_all ? k : a.defer_list[k], ring, coef, crct, lane);
+        decode_general<END, SEG>(a, a.defer_all ? k : a.defer_list[k], ring, coef, crct, lane);
 }
 
 constexpr int kFxThreads = 256; /* k_decode_fx: frames per workgroup (one CRC table copy) */
@@ -996,8 +999,12 @@ hipError_t launch_decode(DecodeArgs a, hipStream_t s) {
     } else {
         a.defer_all = 1; /* rows k_decode_fx cannot read with 16-byte accesses: every frame general */
     }
-    if (a.frame_end) hipLaunchKernelGGL(k_decode<true>, dim3((unsigned)blocks), dim3(kDecThreads), 0, s, a);
-    else hipLaunchKernelGGL(k_decode<false>, dim3((unsigned)blocks), dim3(kDecThreads), 0, s, a);
+    const dim3 gg((unsigned)blocks), gb(kDecThreads);
+    if (a.frame_limit) { /* the batch decoder: a stream end per frame */
+        if (a.frame_end) hipLaunchKernelGGL((k_decode<true, true>), gg, gb, 0, s, a);
+        else hipLaunchKernelGGL((k_decode<false, true>), gg, gb, 0, s, a);
+    } else if (a.frame_end) hipLaunchKernelGGL((k_decode<true, false>), gg, gb, 0, s, a);
+    else hipLaunchKernelGGL((k_decode<false, false>), gg, gb, 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !a.out) return e;
     hipLaunchKernelGGL(k_decorr, dim3((unsigned)a.n_frames), dim3(256), 0, s, a);

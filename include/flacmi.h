@@ -719,6 +719,29 @@ int flacmi_units_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int
                             int32_t tail_len, int32_t sample_size, void* units, int32_t sample_bytes,
                             int64_t unit_stride, int32_t* frame_status, uint32_t* width, void* stream);
 
+/* The frame lists of many streams as one padded planar buffer (k_planar; the third consumer of
+ * the list, for a library of short streams whose samples stay on the device).  frames[n_frames]
+ * is ordered by (stream, first_sample): reserved0 holds the frame's stream index 0 .. n_streams
+ * - 1 and first_sample counts from that stream's first sample; a stream's frames follow one
+ * another without gaps.  Sample t of channel c of stream s goes to
+ * out[(s * channels + c) * pitch + t]: n_streams * channels rows of `elem` at a pitch of `pitch`
+ * elements (a multiple of 16 bytes; out 16-byte aligned).
+ *   FLACMI_PLANAR_INT16    frame_status[f] = FLACMI_STATUS_OVERFLOW where a sample of frame f
+ *                          that the call reads does not fit 16 bits (the frame's samples are
+ *                          then unspecified), else 0;
+ *   FLACMI_PLANAR_INT32    the decoder's int32, no check (the FLACMI_PCM_RAW32 meaning);
+ *   FLACMI_PLANAR_FLOAT32  (float)x * 2^-(sample_size - 1): the int32 rounded to nearest even,
+ *                          then an exact power-of-two scale; sample_size is 4..32.
+ * lengths (device, [n_streams], or NULL: every frame counts) cuts stream s at lengths[s]
+ * samples.  Every element of every row from the stream's length (the end of its last frame,
+ * or lengths[s]) to the pitch is written as 0, a sample no frame holds as 0, samples at or past
+ * the pitch are not read, and nothing outside the n_streams * channels rows is written, whatever
+ * the frame list holds.  Device pointers, enqueued on `stream`. */
+enum flacmi_planar_elem { FLACMI_PLANAR_INT16 = 0, FLACMI_PLANAR_INT32 = 1, FLACMI_PLANAR_FLOAT32 = 2 };
+int flacmi_planar_out_device(flacmi_ctx* ctx, const flacmi_pcm_frame* frames, int64_t n_frames,
+                             int64_t n_streams, int32_t channels, const int64_t* lengths, int32_t sample_size,
+                             int32_t elem, void* out, int64_t pitch, int32_t* frame_status, void* stream);
+
 /* The walk from frame to frame over the candidate table and the first pass's results (plain
  * host code, no device: get_frames' loop, decoder.py:100-108, with each frame's end looked
  * up instead of reached by reading).  status[k] / frame_end[k] are candidate k's results from
@@ -794,6 +817,60 @@ int flacmi_decode_stream_host(flacmi_ctx* ctx, const uint8_t* data, int64_t byte
                               const flacmi_decode_params* dp, int32_t max_block_size, int32_t final_chunk,
                               uint8_t* pcm, int64_t pcm_capacity, int32_t mode, int32_t bytes_per_sample,
                               flacmi_stream_result* res);
+
+/* ---- batch decoder: many whole streams in one call, planar on the device ---------------- */
+/* n_streams whole streams through the steps above, once: data holds their frame regions only
+ * (magic and metadata stripped), stream s being data[seg_offsets[s] .. seg_offsets[s + 1]),
+ * packed back to back (seg_offsets[0] = 0, ascending; an empty region is a stream of no frame).
+ * One copy in, one index and one pass 1 over the whole buffer (every region's first byte joins
+ * the candidates), the walk once per stream over its slice of the table with the region's end as
+ * the stream's end, probes and pass 2 with that end as well.  Each stream decodes exactly as
+ * flacmi_decode_stream_host decodes it alone with final_chunk = 1: a frame its region cuts off
+ * ends it silently, whatever the next region's bytes would complete it to, and the stop of one
+ * stream (results[s].status / site: 0, 0 = none) touches no other.  One dp for the call: the
+ * streams share channels, sample_size, check_crc and the flags.  The rows and the frame list stay
+ * in the context until its next stream, batch or recompress call.  FLACMI_E_UNSUPPORTED when
+ * pass 1's rows would exceed 4 GiB (pass fewer streams), FLACMI_E_INVALID for n_streams < 1 or
+ * seg_offsets that do not start at 0 or descend.
+ *
+ * flacmi_decode_batch_fetch then writes the kept frame list as planar rows (see
+ * flacmi_planar_out_device: elem, pitch in elements, a multiple of 16 bytes and at least the
+ * longest stream's samples) into out[n_streams][channels][pitch]: a device buffer, written on
+ * `stream`, or with host_out != 0 host memory (synchronous; `stream` ignored).  With
+ * FLACMI_PLANAR_INT16 a frame holding a sample outside 16 bits stops its stream there like
+ * FLACMI_DSITE_PCM_RANGE in the stream decoder (the call waits for the kernel, and writes the
+ * affected rows again): results[n_streams] (optional) receives the streams' final frames,
+ * samples, consumed, status and site.  Every element from a stream's final length to the pitch
+ * is 0.
+ *
+ * Ordering: flacmi_decode_batch_host is synchronous on the context's own stream.  A fetch into a
+ * device buffer with FLACMI_PLANAR_INT32 or FLACMI_PLANAR_FLOAT32 only enqueues k_planar on
+ * `stream`, and that kernel reads the context's rows: the caller must have synchronised `stream`
+ * (or otherwise know the kernel finished) before the context's next stream, batch or recompress
+ * call, which reuses or frees those rows on the context's stream without waiting for `stream`, and
+ * before flacmi_destroy.  The FLACMI_PLANAR_INT16 and host_out fetches return with the rows
+ * written. */
+typedef struct flacmi_batch_stream_result {
+    int64_t frames;          /* frames delivered */
+    int64_t samples;         /* samples per channel delivered */
+    int64_t consumed;        /* offset in data after the last delivered frame */
+    int32_t status, site;    /* why the stream stopped: 0, 0 = it has not (its end, or a cut-off frame) */
+    int64_t probes;          /* as flacmi_stream_result, this stream's */
+    int64_t pass2_frames;
+    int64_t reserved[2];
+} flacmi_batch_stream_result;
+typedef struct flacmi_batch_summary {
+    int64_t candidates;      /* k_index's count over the whole buffer */
+    int64_t frames;          /* frames delivered, all streams */
+    int64_t max_samples;     /* the longest stream's samples per channel */
+    int64_t probes, pass2_frames;
+    int64_t reserved[3];
+} flacmi_batch_summary;
+int flacmi_decode_batch_host(flacmi_ctx* ctx, const uint8_t* data, const int64_t* seg_offsets, int64_t n_streams,
+                             const flacmi_decode_params* dp, int32_t max_block_size,
+                             flacmi_batch_stream_result* results, flacmi_batch_summary* summary);
+int flacmi_decode_batch_fetch(flacmi_ctx* ctx, void* out, int64_t pitch, int32_t elem, int32_t host_out,
+                              flacmi_batch_stream_result* results, void* stream);
 
 /* ---- recompress: .flac bytes in, .flac frames out, the samples stay on the device ------- */
 /* One chunk of a stream through the decoder above (steps copy in .. pass 2, same arguments:
